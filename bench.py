@@ -18,6 +18,12 @@ Multi GPU:   python -m torch.distributed.run --nproc-per-node N --master-addr 12
 Scaling is weak: the per-GPU micro-batch is fixed, global batch = N x micro-batch.
 Reference to beat: 62 661 rows/s (TF 2.0 on a laptop CPU).
 
+A plain run sets up, settles, warms up, times the K steps and prints the headline line.
+``--full`` adds every side measurement after the headline (per-event scoring latency, Kafka
+and MQTT end to end, the Keras batch-32 and fit paths, streams, the LSTM configs; at N > 1
+the collectives and the in-kernel DP), each under the ``--budget-s`` guard, in the same line.
+``--dump-outputs DIR`` writes the state the last timed step left (``dump_outputs``).
+
 Clock settle: before the W warm-up steps, full training steps run untimed for
 ``--settle-ms`` (default 100 ms).  A GPU coming out of idle goes through a power /
 clock-management transient lasting ~40 dispatches (~30 ms) of this kernel: per-step time
@@ -81,7 +87,16 @@ def parse():
     p.add_argument("--seed", type=int, default=0)
     p.add_argument("--settle-ms", type=float, default=100.0,
                    help="untimed steps before the warm-up until this much GPU time has passed (DPM clock settle)")
-    p.add_argument("--headline-only", action="store_true", help="skip every side measurement")
+    p.add_argument("--full", action="store_true",
+                   help="after the headline, run every side measurement (scoring latency, Kafka / MQTT end to end, "
+                        "batch-32 and fit paths, streams, LSTM, N > 1: collectives and in-kernel DP) and report them "
+                        "in the line; without it the run is the headline alone")
+    p.add_argument("--headline-only", action="store_true",
+                   help="with --full: skip every side measurement all the same (the phases are named as skipped)")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="after the timed steps write what the last step left with the caller -- parameter image, "
+                        "Adam moments, metric accumulators, step / ring counters -- as DIR/<name>.npy (rank 0); the "
+                        "W + K steps then start from the seeded model again, so the arrays depend on the arguments alone")
     p.add_argument("--budget-s", type=float, default=450.0,
                    help="wall-clock budget of the whole run (from process start): a side measurement starts only "
                         "if its estimate still fits; past budget + 60 s a watchdog prints the line and ends the job")
@@ -490,6 +505,20 @@ def measure_batch32_fleet(spec, data, device, steps, scale, shift, n_models=1024
             "path": "fleet mode of ae_minibatch.hip (one workgroup per independent model), 1 GPU"}
 
 
+def dump_outputs(path: str, fused) -> None:
+    """``--dump-outputs``: what ``step_ring`` leaves with its caller after the last timed step, one
+    ``.npy`` per array (a few KB in all): the parameter image and Adam moments (float32, as on the
+    device), the epoch metric accumulators (sum squared error, sum |h1|, correct argmax, rows) and
+    the optimizer-step / ring-cursor counters (float64: exact for these integers)."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    arrays = {"params": fused.params, "adam_m": fused.m, "adam_v": fused.v,
+              "metrics": fused.metrics.double(), "counters": torch.cat([fused.iter, fused.cursor]).double()}
+    for name, t in arrays.items():
+        np.save(os.path.join(path, f"{name}.npy"), t.detach().cpu().numpy())
+
+
 def self_launch(args) -> int | None:
     """``--gpus N > 1`` without a launcher: run N ranks under ``torch.distributed.run`` as a
     CHILD process (never an exec, and before anything touches the GPU), relay its output
@@ -572,6 +601,10 @@ def main():
     torch.cuda.synchronize()
     pack_ms = (time.perf_counter() - tp) * 1e3
 
+    # --dump-outputs: the settle below runs for a time, not a step count, so it leaves the model at
+    # a state that differs from run to run; the dump run puts the initial state back after it
+    params0 = fused.params.clone() if args.dump_outputs else None
+
     def eager_step():
         fused.step_ring(global_batch=gb, allreduce=allreduce)
 
@@ -614,6 +647,10 @@ def main():
                 el = dp.allreduce_max(el, device)   # one decision for all ranks (collectives stay paired)
             if el >= args.settle_ms:
                 break
+    if params0 is not None:   # the W + K steps that follow start from the seeded model at ring row 0
+        fused.params.copy_(params0)
+        for t in (fused.m, fused.v, fused.iter, fused.cursor, fused.metrics):
+            t.zero_()
     run(args.warmup, 0)
     dp.barrier(device)
     torch.cuda.synchronize()
@@ -627,6 +664,8 @@ def main():
     metrics = fused.read_metrics()
     if args.dump_params:
         np.save(f"{args.dump_params}.rank{rank}.npy", fused.params.detach().cpu().numpy())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, fused)
     # per-rank timed-region spread (the headline uses the max)
     spread = gather_all([t1 - t0], device)
     step_ms = [v[0] / args.steps * 1e3 for v in spread]
@@ -673,6 +712,11 @@ def main():
         "final_epoch_loss": metrics["loss"],
         "final_accuracy": metrics["accuracy"],
     }
+    if not args.full:   # a plain run is the headline alone: no side measurement, no watchdog process
+        if rank == 0:
+            print(json.dumps(ordered_line(out)), flush=True)
+        dp.shutdown()
+        return
     ph = Phases(args.budget_s, rank, world, device, out)
     ph.phase_s["startup_to_headline"] = round(time.time() - T_PROC, 3)
     ph.start_watchdog()        # rank 0: from here on the line cannot be lost (bench/_watchdog.py)

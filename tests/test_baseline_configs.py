@@ -43,8 +43,8 @@ def test_config1_cpu_autoencoder_on_reference_csv():
 
 @pytest.mark.gpu
 def test_config2_bench_contract(cuda_device):
-    r = subprocess.run([sys.executable, "bench.py", "--steps", "3", "--warmup", "1", "--batch-per-gpu", "1048576",
-                        "--dataset-rows", "4194304", "--infer-events", "50"], cwd=ROOT, capture_output=True,
+    r = subprocess.run([sys.executable, "bench.py", "--full", "--steps", "3", "--warmup", "1", "--batch-per-gpu",
+                        "1048576", "--dataset-rows", "4194304", "--infer-events", "50"], cwd=ROOT, capture_output=True,
                        text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-3000:]
     out = _json_line(r.stdout)

@@ -44,7 +44,7 @@ def test_bench_two_ranks_shared_gpu(tmp_path, cuda_device):
     dump = str(tmp_path / "params")
     # no torchrun prefix: bench.py must launch its own ranks (the driver runs it this way)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"),
-           "--gpus", "2", "--steps", "4", "--warmup", "2", "--batch-per-gpu", "65536",
+           "--gpus", "2", "--full", "--steps", "4", "--warmup", "2", "--batch-per-gpu", "65536",
            "--dataset-rows", "262144", "--infer-events", "2000", "--infer-repeats", "1", "--e2e-events", "0",
            "--lstm-steps", "0", "--batch32-steps", "2000", "--mqtt-clients", "0", "--large-stream-rows", "400000",
            "--stream-dp-rows", "150000", "--stream-dp-batch", "16384", "--dump-params", dump]
@@ -92,7 +92,7 @@ def test_bench_n_ranks_rehearsal(tmp_path, cuda_device, n):
     env = dict(os.environ, SML_SHARE_GPU0="1", OMP_NUM_THREADS="2")
     dump = str(tmp_path / "params")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"),
-           "--gpus", str(n), "--steps", "4", "--warmup", "2", "--batch-per-gpu", "65536",
+           "--gpus", str(n), "--full", "--steps", "4", "--warmup", "2", "--batch-per-gpu", "65536",
            "--dataset-rows", "262144", "--infer-events", "2000", "--infer-repeats", "1", "--e2e-events", "2000",
            "--batch32-steps", "2000", "--fleet-models", "64", "--dp-steps", "500", "--collective-iters", "50",
            "--fit-epochs", "2", "--fresh-steps", "2", "--fit-rows", "200000", "--stream-rows", "500000",
@@ -138,8 +138,8 @@ def test_bench_budget_skips_and_still_prints(cuda_device):
     headline line still prints."""
     env = dict(os.environ, OMP_NUM_THREADS="2")
     env.pop("SML_SHARE_GPU0", None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--batch-per-gpu",
-           "65536", "--dataset-rows", "131072", "--budget-s", "1"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "3", "--warmup", "1",
+           "--batch-per-gpu", "65536", "--dataset-rows", "131072", "--budget-s", "1"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=240, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
@@ -154,8 +154,8 @@ def test_bench_force_pg_rccl_world1(cuda_device):
     per-step all-reduce in the timed loop, P2P exchange + in-kernel DP, collectives."""
     env = dict(os.environ, SML_FORCE_PG="1", OMP_NUM_THREADS="2")
     env.pop("SML_SHARE_GPU0", None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "2",
-           "--batch-per-gpu", "65536", "--dataset-rows", "262144", "--infer-events", "1000", "--infer-repeats", "1",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--full", "--steps", "4",
+           "--warmup", "2", "--batch-per-gpu", "65536", "--dataset-rows", "262144", "--infer-events", "1000", "--infer-repeats", "1",
            "--e2e-events", "0", "--lstm-steps", "0", "--batch32-steps", "2000", "--fit-rows", "0",
            "--stream-rows", "0", "--large-stream-rows", "0", "--dp-steps", "2000", "--collective-iters", "50",
            "--mqtt-clients", "0"]

@@ -17,7 +17,7 @@ for c in SQ_WAVES SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_BUSY_CU_CYCLES SQ_WAVE_CY
   if have "$c" && [ "$(echo $SQ | wc -w)" -lt 8 ]; then SQ="$SQ $c"; fi
 done
 echo "SQ pass counters:$SQ"
-BENCH="python3 $R/bench.py --steps 5 --warmup 2 --fleet-models 0 --batch32-steps 0 --dp-steps 0 --fit-rows 0 --stream-rows 0 --infer-events 100"
+BENCH="python3 $R/bench.py --full --steps 5 --warmup 2 --fleet-models 0 --batch32-steps 0 --dp-steps 0 --fit-rows 0 --stream-rows 0 --infer-events 100"
 run() {  # run <name> <regex> <counters...> -- <cmd>
   local name=$1 rx=$2; shift 2
   local pmc=()

@@ -7,7 +7,7 @@ mkdir -p "$O"
 export TMPDIR=/tmp
 step() { local n=$1 t=$2; shift 2; echo "== $n ($(date +%T))"; timeout -k 10 "$t" "$@" > "$O/$n.log" 2>&1; local rc=$?;
          tail -n 2 "$O/$n.log" | cut -c1-400; [ $rc -eq 0 ] || { echo "FAILED $n rc=$rc"; exit $rc; }; }
-[ -n "${SKIPBENCH:-}" ] || step bench 500 python "$R/bench.py"
+[ -n "${SKIPBENCH:-}" ] || step bench 500 python "$R/bench.py" --full
 cd /tmp
 step prof_head 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/prof_head" -o run \
     -- python3 "$R/bench.py" --headline-only --steps 20 --warmup 5

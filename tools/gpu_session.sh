@@ -30,10 +30,10 @@ for s in $STEPS; do
     testsel) step pytest_sel 600 python -u -m pytest ${TESTS:-tests} -m gpu -x -v -p no:cacheprovider --timeout 120 --timeout-method thread ;;
     fit) step bench_fit 600 python bench/bench_fit.py ${FIT_ARGS:-} ;;
     smoke) step smoke 300 python -c "import __graft_entry__ as g; g.smoke()" ;;
-    bench) step bench 600 python bench.py ${BENCH_ARGS:-} ;;
+    bench) step bench 600 python bench.py --full ${BENCH_ARGS:-} ;;
     prof)
       (cd /tmp && step rocprof 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof" -o run -- \
-          python3 "$ROOT/bench.py" --steps 50 --warmup 5 --infer-events 100 ${BENCH_ARGS:-}) ;;
+          python3 "$ROOT/bench.py" --full --steps 50 --warmup 5 --infer-events 100 ${BENCH_ARGS:-}) ;;
     lstm) step bench_lstm 600 python bench/bench_lstm.py ${LSTM_ARGS:-} ;;
     infer) step bench_infer 600 python bench/bench_infer.py ${INFER_ARGS:-} ;;
     ingest) step bench_ingest 900 python bench/bench_ingest.py ${INGEST_ARGS:-} ;;
