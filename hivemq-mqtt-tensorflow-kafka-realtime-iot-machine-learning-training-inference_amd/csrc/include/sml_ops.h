@@ -14,7 +14,8 @@ int ae_train_grid(int64_t n, int max_blocks);
 hipError_t ae_train_launch(const float* x, int64_t n, int64_t ld, const float* scale, const float* shift,
                            const float* params, float* partials, int64_t* iter, const int64_t* cursor,
                            const int* dims, const int* acts, float l1, int want_acc, int grid, const uint8_t* xpack,
-                           hipStream_t stream, int* grid_used);  // grid_used <= grid: slabs written
+                           hipStream_t stream, int* grid_used,   // grid_used <= grid: slabs written
+                           unsigned xpack_live = 0);  // features the packed ring stores (0: all D)
 // metrics (optional, 4 floats): += (sum sq err, sum |h1|, correct argmax, rows) -- evaluate()
 hipError_t ae_forward_launch(const float* x, int64_t n, int64_t ld, const float* scale, const float* shift,
                              const float* params, float* recon, float* score, uint8_t* flag, float threshold,
@@ -170,7 +171,12 @@ bool lstm_fused_frag_supported(int U, int IN, bool x_bf16, bool want_dx);
 // fused into the pack with no permutation array)
 hipError_t pack_tiles_argmax_launch(const float* x, int64_t n, int64_t ld, int D, const float* scale,
                                     const float* shift, uint8_t* out, hipStream_t stream,
-                                    const int64_t* index = nullptr, uint64_t perm_key = 0, int64_t perm_n = 0);
+                                    const int64_t* index = nullptr, uint64_t perm_key = 0, int64_t perm_n = 0,
+                                    uint64_t live_mask = 0);
+// live_mask (0 or all D bits: the layout above): the compact layout -- per tile 16 rows x
+// popcount(live_mask) floats, the live features in ascending order, then the same 16 argmax
+// bytes (over all D values, original numbering); n/16 * (64*popcount + 16) bytes.  The features
+// left out must be the ones the normaliser zeroes; they count as the constant 0 in the argmax.
 // out[i] = perm_row(start + i, n, key): the same bijection, materialised (short batches, tests)
 hipError_t perm_indices_launch(int64_t* out, int64_t start, int64_t count, int64_t n, uint64_t key,
                                hipStream_t stream);

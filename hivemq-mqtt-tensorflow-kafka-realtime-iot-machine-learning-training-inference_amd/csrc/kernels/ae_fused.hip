@@ -28,6 +28,10 @@
 //    accumulators are folded into the image when the slab is written (packed_fold_src).
 //    The loop is issue-bound: this cut VALU 27 %, LDS 31 %, SALU 40 % per row against
 //    the one-tile loop (SML_AE_ILP=1), 37 -> 47 G rows/s (profiles/r02/ilp).
+//  * the cardata normaliser zeroes four of the 18 features, so its packed ring stores the 14
+//    live ones (compact ring, CM variants of the packed-pair loop): 57 instead of 73 B per
+//    row from HBM and through LDS.  The compute is the 18-column loop's, operand for operand,
+//    so the results are bit-identical to it (profiles/r07/compact_ring).
 //
 // Padded parameter image (fp32, 1536 floats), row-major [in][out]:
 //   L1 [32][16] @0    (bias = row 31)     requires D  <= 31, n1 <= 15
@@ -834,6 +838,37 @@ __device__ __forceinline__ void train_tiles_ilp(const AEArgs& a, const Frags& F,
 //   operand (the other tile's half zeroed); dW3 is the diagonal blocks of ONE contraction.
 //   The accumulators hold both tiles' halves side by side and are folded into the parameter
 //   image once per launch (packed_fold_src).  Needs n2, n3 <= 7.
+//
+// Compact ring (CM, pack_tiles_argmax with a live mask): the reference's normalize_fn assigns
+// the constant 0 to features 0, 2, 4 and 5 (cardata NORMALIZE_RANGES None), so the packed ring
+// stores only the 14 live ones, in ascending feature order (compact float k: feature 1, 3, 6,
+// 7, ..., 17).  The loop keeps the 18-column operand layout -- lane (c, g) holds inputs
+// 4g..4g+3 of row c, inputs 16 / 17 come as UP -- and only reads them from other places:
+//   g = 0: inputs (0, 1, 2, 3)   <- (*, k0, *, k1)      g = 2: inputs 8..11  <- k4..k7
+//   g = 1: inputs (4, 5, 6, 7)   <- (*, *, k2, k3)      g = 3: inputs 12..15 <- k8..k11
+// as four consecutive floats of the row from ONE lane offset (cm_off), g = 0 moving its k0 / k1
+// into place with two selects.  A dead slot `*` holds whatever float of the same row came along
+// (always landed, always finite -- nothing outside the row is read): its layer-1
+// weight row is zeroed in the fragment (the 18-column loop multiplies a zero input by the
+// weight, this one a finite input by zero: both products are 0), its dW1 row is written as the
+// exact 0 it is (packed_fold_src), and the loss selects 0 as its target.  Everything else is
+// the same instruction on the same operands, so the results are the 18-column loop's.
+constexpr unsigned kLiveCardata = 0x3FFFFu & ~((1u << 0) | (1u << 2) | (1u << 4) | (1u << 5));
+__host__ __device__ constexpr bool cm_dead(int f) { return f == 0 || f == 2 || f == 4 || f == 5; }
+// byte offset, from the row's first compact float, of the lane's four floats: g = 0 and g = 1
+// read k0..k3, g = 2 k4..k7, g = 3 k8..k11
+__device__ __forceinline__ int cm_off(int g) { return g < 2 ? 0 : g == 2 ? 16 : 32; }
+// the lane's inputs 4g..4g+3 of one compact row (dead slots: finite don't-cares)
+__device__ __forceinline__ f32x4 cm_row_x(const char* row, int g) {
+  typedef __attribute__((address_space(3))) const f32x2_t lds_f2;
+  const f32x2_t a = *(lds_f2*)(row + cm_off(g)), b = *(lds_f2*)(row + cm_off(g) + 8);
+  return f32x4{a[0], g == 0 ? a[0] : a[1], b[0], g == 0 ? a[1] : b[1]};   // g = 0: inputs 1 / 3 are k0 / k1
+}
+// the same with the dead inputs as the constant 0 they are (the loss's targets)
+__device__ __forceinline__ f32x4 cm_zero_dead(f32x4 x, int g) {
+  return f32x4{g < 2 ? 0.f : x[0], g == 1 ? 0.f : x[1], g == 0 ? 0.f : x[2], x[3]};
+}
+
 struct FragsP {
   bf16x4 w1t;         // L1 forward from inputs 0..15 (prescaled)
   bf16x4 w1u[2];      // L1 forward [tile] from the UP inputs 16 / 17 and the constant-1 bias input
@@ -855,13 +890,15 @@ struct FragsP {
 
 __device__ __forceinline__ int img_row_of_packed(int i) { return i == 7 ? 15 : i; }   // i = packed % 8
 
+template <bool CM = false>
 __device__ __forceinline__ void load_frags_packed(const AEArgs& a, int c, int g, FragsP& F) {
   const float* P = a.params;
   const float k1 = kTanhExp2;
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
     const int k = 4 * g + j;
-    F.w1t[j] = bfbits(k1 * ldsel(P, k < a.D && c < a.n1, OFF1 + k * 16 + c));
+    // CM: the dead inputs' slots hold don't-care floats, so their weight rows are 0 here
+    F.w1t[j] = bfbits(k1 * ldsel(P, k < a.D && c < a.n1 && !(CM && cm_dead(k)), OFF1 + k * 16 + c));
     // L1 from UP: B row k = 4q (j = 0) is input 16 + (q & 1) of tile q >> 1, k = 1 (g = 0, j = 1)
     // the constant 1 of the bias; bias slot 15's output is injected there (tanh_exp2(256) = 1)
 #pragma unroll
@@ -945,9 +982,15 @@ __device__ __forceinline__ void load_frags_packed(const AEArgs& a, int c, int g,
 }
 
 // Image slot s -> the packed-accumulator slab slots whose sum it is (-1: none, gradient 0).
+// CM: the dead inputs' layer-1 rows accumulated don't-care inputs; their gradient is exactly 0.
+template <bool CM = false>
 __device__ __forceinline__ void packed_fold_src(int s, int& s1, int& s2) {
   s1 = s;
   s2 = -1;
+  if (CM && s < OFF1 + 16 * 16 && cm_dead((s - OFF1) >> 4)) {
+    s1 = -1;
+    return;
+  }
   if (s >= OFF1 + 16 * 16 && s < OFF2) {   // layer-1 rows 16..31: UP rows 16 + m of the slab
     const int in = (s - OFF1) >> 4, out = (s - OFF1) & 15;
     if (in == 16 || in == 17) {
@@ -1018,7 +1061,9 @@ __device__ __forceinline__ bf16x4 tr_read(char* slot, int c, int g) {
 // ring slot at the output layer instead of being held in 9 registers across the whole forward
 // chain (`xring[p]`: the pair's slot base; the slot is only re-filled after the next iteration's DMA
 // issue).  The ring's rows are the normalised ones, bit-identical to the first read.
-template <int PACK, int DC, bool TP, int TS = 10, int NP = 1, int XP = 0, bool RX = false>
+// CM (compact ring): xf's dead-input slots are don't-cares (see cm_row_x); the RX re-read takes
+// the compact offsets and the loss masks the dead slots' targets to 0.
+template <int PACK, int DC, bool TP, int TS = 10, int NP = 1, int XP = 0, bool RX = false, bool CM = false>
 __device__ __forceinline__ void train_pair_packed(const AEArgs& a, const FragsP& F, char* scr, int c, int g,
                                                   const f32x4 (&xf)[NP][2][2], const float (&xup)[NP],
                                                   const int (&ix)[NP][2], f32x4 acc1[2], f32x4& acc2, f32x4& acc3,
@@ -1118,18 +1163,26 @@ __device__ __forceinline__ void train_pair_packed(const AEArgs& a, const FragsP&
     if constexpr (RX) {
       typedef __attribute__((address_space(3))) const f32x2_t lds_f2;
       typedef __attribute__((address_space(3))) const float lds_f;
-      constexpr int SLOTB = 64 * 18 + 16;
+      constexpr int DR = CM ? 14 : 18, SLOTB = 64 * DR + 16;
 #pragma unroll
       for (int u = 0; u < 2; ++u) {
-        const char* row = xring[p] + u * SLOTB + c * 4 * 18 + 16 * g;
-        const f32x2_t v0 = *(lds_f2*)row, v1 = *(lds_f2*)(row + 8);
-        xl[p][u] = f32x4{v0[0], v0[1], v1[0], v1[1]};
+        if constexpr (CM) {
+          xl[p][u] = cm_row_x(xring[p] + u * SLOTB + c * 4 * DR, g);
+        } else {
+          const char* row = xring[p] + u * SLOTB + c * 4 * 18 + 16 * g;
+          const f32x2_t v0 = *(lds_f2*)row, v1 = *(lds_f2*)(row + 8);
+          xl[p][u] = f32x4{v0[0], v0[1], v1[0], v1[1]};
+        }
       }
-      xul[p] = *(lds_f*)(xring[p] + c * 4 * 18 + 4 * (16 + (g & 1)) + (g >= 2 ? SLOTB : 0));
+      xul[p] = *(lds_f*)(xring[p] + c * 4 * DR + 4 * (DR - 2 + (g & 1)) + (g >= 2 ? SLOTB : 0));
     } else {
 #pragma unroll
       for (int u = 0; u < 2; ++u) xl[p][u] = xf[p][u][0];
       xul[p] = xup[p];
+    }
+    if constexpr (CM) {
+#pragma unroll
+      for (int u = 0; u < 2; ++u) xl[p][u] = cm_zero_dead(xl[p][u], g);
     }
   }
 #pragma unroll
@@ -1324,43 +1377,49 @@ __device__ __forceinline__ void train_pair_packed(const AEArgs& a, const FragsP&
 // Packed pairs (ILP 3) at OCC >= 4: two pair slots (4 x 1168 B) per wave.
 template <int OCC, int ILP = 1>
 constexpr int ring_bytes() { return ILP == 3 ? (OCC >= 4 ? 4672 : 7008) : OCC >= 4 ? 3968 : (ILP >= 2 ? 7008 : 6144); }
-// packed pairs: PF tiles of 64 * 18 + 16 B (sized by the ring depth, not the occupancy)
-template <int OCC, int ILP, int PF>
-constexpr int ring_bytes_pf() { return ILP == 3 ? PF * 1168 : ring_bytes<OCC, ILP>(); }
+// packed pairs: PF tiles of 64 * 18 + 16 B (sized by the ring depth, not the occupancy);
+// compact ring (CM): 64 * 14 + 16 = 912 B per tile
+template <int OCC, int ILP, int PF, int CM = 0>
+constexpr int ring_bytes_pf() { return ILP == 3 ? PF * (CM ? 912 : 1168) : ring_bytes<OCC, ILP>(); }
 
 // LDS layout.  Default: [slab area = per-wave transpose scratch (10 x 512 B) | normaliser | rings].
 // Packed pairs (ILP 3): [TS x 512 B transpose scratch per wave | normaliser | rings], and the
 // per-wave gradient slabs written after the loop ALIAS that whole area (the rings are retired
 // with vmcnt(0) and a workgroup barrier first) -- so the loop's LDS is not charged for the slab:
 // OCC 4 (two pair slots, TS 10) is 39 424 B = four workgroups per CU.
-template <int PF, int OCC, int ILP, int TS, int NPW = 1>
+template <int PF, int OCC, int ILP, int TS, int NPW = 1, int CM = 0>
 struct AELds {
   static constexpr int SCR = (ILP == 3 ? NPW * TS : 10) * 512;      // per wave (0: MFMA transposes)
   static constexpr int NORM_OFF = ILP == 3 ? WAVES * SCR : SLAB_BYTES;
   static constexpr int RING_OFF = NORM_OFF + NORM_BYTES;
-  static constexpr int RING = ring_bytes_pf<OCC, ILP, PF>();
+  static constexpr int RING = ring_bytes_pf<OCC, ILP, PF, CM>();
   static constexpr int END = RING_OFF + (PF > 0 ? WAVES * RING : 0);
   static constexpr int BYTES = END > SLAB_BYTES ? END : SLAB_BYTES;
 };
 
 // NPW (packed pairs only): pairs trained per loop iteration in one interleaved stream.
 // XP (packed pairs only): the weight-gradient operand path of train_pair_packed.
+// CM (packed pairs on the tile-packed ring only): the compact ring of the 14 live cardata
+// features: 912-B tile slots, a pair = two DMAs of 1024 + 800 B.
 template <int PACK, bool VEC, int PF, int OCC, int DC = 0, int XM = 0, int ILP = 1, int TS = 10, int NPW = 1,
-          int XP = 0>
+          int XP = 0, int CM = 0>
 __global__ __launch_bounds__(WAVES * 64, OCC) void ae_train_kernel(AEArgs a) {
   constexpr bool FAST = zero_preserving<PACK>();
-  using L = AELds<PF, OCC, ILP, (XP == 2 ? 0 : TS), NPW>;
+  constexpr bool CMP = CM != 0;
+  static_assert(!CMP || (ILP == 3 && XM == 1 && DC == 18), "compact ring: packed pairs, tile-packed ring, D = 18");
+  constexpr int DR = CMP ? 14 : DC;   // floats per ring row (0: a.D)
+  using L = AELds<PF, OCC, ILP, (XP == 2 ? 0 : TS), NPW, CM>;
   static_assert(NPW == 1 || ILP == 3, "several pairs per iteration: packed pairs only");
   constexpr int RING = L::RING;
   static_assert(WAVES * 10 * 512 <= SLAB_BYTES, "transpose scratch must fit in the slab buffer");
   static_assert(ILP == 3 || TS == 10, "shared transpose slots: packed pairs only");
-  static_assert(PF == 0 || PF * 64 * 17 <= RING, "ring slots must fit the smallest ring tile");
+  static_assert(PF == 0 || CMP || PF * 64 * 17 <= RING, "ring slots must fit the smallest ring tile");
   // XM: x-argmax mode. 0 in-kernel argmax; 1 tile-packed ring (rows + ingest-time argmax
   // bytes per tile, pack_tiles_argmax); 2 / 3 A/B probes that skip the argmax of x entirely (wrong accuracy, timing
   // only: 2 with the plain tile order, 3 with the chunked order) -- they separate the VALU
   // saving from the cost of delivering the bytes (profiles/r02/SUMMARY.md)
   constexpr bool XA = XM != 0;
-  static_assert(XM != 1 || (DC > 0 && PF > 0 && PF * (64 * DC + 16) <= RING), "XA: compile-time D, ring slots + argmax");
+  static_assert(XM != 1 || (DC > 0 && PF > 0 && PF * (64 * DR + 16) <= RING), "XA: compile-time D, ring slots + argmax");
   // one LDS array: per-wave transpose scratch during the tile loop, per-wave
   // gradient slabs afterwards | the normaliser | (PF > 0) the per-wave input rings
   __shared__ __attribute__((aligned(16))) float smem[L::BYTES / 4];
@@ -1371,7 +1430,7 @@ __global__ __launch_bounds__(WAVES * 64, OCC) void ae_train_kernel(AEArgs a) {
   const char* norm = reinterpret_cast<const char*>(smem) + L::NORM_OFF;
   if (a.cursor) {  // streaming ring consumer (uniform scalar load)
     a.x += a.cursor[0] * a.ld;
-    if (XM == 1) a.xpack += (a.cursor[0] >> 4) * (int64_t)(64 * a.D + 16);
+    if (XM == 1) a.xpack += (a.cursor[0] >> 4) * (int64_t)(64 * (CMP ? DR : a.D) + 16);
   }
 
   if (a.iter && blockIdx.x == 0 && threadIdx.x == 0) a.iter[0] += 1;
@@ -1383,7 +1442,7 @@ __global__ __launch_bounds__(WAVES * 64, OCC) void ae_train_kernel(AEArgs a) {
   Frags F;
   FragsP FP;   // ILP 3 (packed pairs) only
   if constexpr (ILP == 3)
-    load_frags_packed(a, c, g, FP);
+    load_frags_packed<CMP>(a, c, g, FP);
   else
     load_frags<FAST, FAST && prescaled_tanh<PACK>(), FAST && inject_bias_slots<PACK>()>(a, c, g, F, true);
   const float pad1 = (g == 3) ? 1.0f : 0.0f;
@@ -1401,7 +1460,7 @@ __global__ __launch_bounds__(WAVES * 64, OCC) void ae_train_kernel(AEArgs a) {
     // LDS-DMA ring: tile first + k*stride lives in slot k % PF.  Every issue is
     // exactly two VMEM instructions (tiles past the end are clamped to the last
     // full tile, never skipped), so "tile k landed" is vmcnt(2 * (PF - 1)).
-    const int slotb = 64 * (DC > 0 ? DC : a.D) + (XM == 1 ? 16 : 0);   // compile-time with DC: immediate offsets
+    const int slotb = 64 * (DR > 0 ? DR : a.D) + (XM == 1 ? 16 : 0);   // compile-time with DC: immediate offsets
     constexpr int NV = 2;  // VMEM instructions per tile issue
     const int nl2 = (slotb - 1024) >> 4;  // lanes of the second 16-B-per-lane DMA (>= 4)
     const int uwid = __builtin_amdgcn_readfirstlane(wid);  // keep the ring bookkeeping scalar
@@ -1442,7 +1501,12 @@ __global__ __launch_bounds__(WAVES * 64, OCC) void ae_train_kernel(AEArgs a) {
                       "tile pairs: tile-packed ring (or raw rows, packed pairs), plain order");
         auto ring_tile = [&](int slot, f32x4 xf[2], int& ix) {
           typedef __attribute__((address_space(3))) const unsigned char lds_u8;
-          if constexpr (XM == 1) ix = (int)*(lds_u8*)(ring + slot * slotb + 64 * a.D + c);
+          if constexpr (XM == 1) ix = (int)*(lds_u8*)(ring + slot * slotb + (slotb - 16) + c);
+          if constexpr (CMP) {   // the same inputs 0..15 from the compact row
+            xf[0] = cm_row_x(ring + slot * slotb + c * 4 * DR, g);
+            xf[1] = f32x4{0.f, 0.f, 0.f, 0.f};
+            return;
+          }
           if constexpr (ILP == 3) {   // inputs 0..15 only (16 / 17 come as UP, ring_up)
             typedef __attribute__((address_space(3))) const f32x2_t lds_f2;
             const char* row = ring + slot * slotb + c * 4 * a.D + 16 * g;
@@ -1460,7 +1524,7 @@ __global__ __launch_bounds__(WAVES * 64, OCC) void ae_train_kernel(AEArgs a) {
         // tile 1 of a pair sits in the next slot (pairs start on even slots, PF even), so one
         // loop-invariant lane offset covers both tiles
         static_assert(ILP != 3 || PF % 2 == 0, "pairs start on even ring slots");
-        const int up_off = c * 4 * DC + 4 * (16 + (g & 1)) + (g >= 2 ? slotb : 0);
+        const int up_off = c * 4 * DR + 4 * (DR - 2 + (g & 1)) + (g >= 2 ? slotb : 0);   // CM: compact floats 12 / 13
         auto ring_up = [&](int slot) -> float {   // slot: the pair's first tile
           typedef __attribute__((address_space(3))) const float lds_f;
           return *(lds_f*)(ring + slot * slotb + up_off);
@@ -1470,9 +1534,10 @@ __global__ __launch_bounds__(WAVES * 64, OCC) void ae_train_kernel(AEArgs a) {
           // the tile-packed ring, moved by three LDS-DMAs (64 + 64 + 18 lanes x 16 B) instead of
           // two per tile; pairs are interleaved over the waves.  The launcher guarantees an even
           // tile count (no half pair).  Ring: PF / 2 pair slots, one pair in flight per slot.
-          constexpr int PS = PF / 2, NVP = 3;
+          // Compact ring: a pair is 2 x 912 B, two DMAs (64 + 50 lanes x 16 B).
+          constexpr int PS = PF / 2, NVP = CMP ? 2 : 3;
           const int pairb = 2 * slotb;
-          const int nl3 = (pairb - 2048) >> 4;   // lanes of the third DMA
+          const int nl3 = (pairb - (CMP ? 1024 : 2048)) >> 4;   // lanes of the last DMA
           const int64_t npairs = nfull >> 1;
           auto issue_pair = [&](int64_t pi, int ps) {
             pi = pi < npairs ? pi : npairs - 1;   // prefetch past the end re-reads the last pair
@@ -1482,8 +1547,12 @@ __global__ __launch_bounds__(WAVES * 64, OCC) void ae_train_kernel(AEArgs a) {
                               pi * pairb;
             const unsigned dst = ring_lds + ps * pairb;
             glds16(src, voff, dst);
-            glds16(src + 1024, voff, dst + 1024);
-            if (lane < nl3) glds16(src + 2048, voff, dst + 2048);
+            if constexpr (CMP) {
+              if (lane < nl3) glds16(src + 1024, voff, dst + 1024);
+            } else {
+              glds16(src + 1024, voff, dst + 1024);
+              if (lane < nl3) glds16(src + 2048, voff, dst + 2048);
+            }
           };
           // NPW pairs per iteration (pi, pi + stride, ...): the ring holds PS = PF / 2 pair slots, PS - NPW
           // of them in flight while the NPW oldest are trained on.
@@ -1536,8 +1605,8 @@ __global__ __launch_bounds__(WAVES * 64, OCC) void ae_train_kernel(AEArgs a) {
               rs = rs + 1 == PS ? 0 : rs + 1;
             }
             constexpr bool RX = XM == 1 && OCC >= 4;
-            train_pair_packed<PACK, DC, false, TS, NPW, XP, RX>(a, FP, scr, c, g, xf, xup, ix, acc1, acc2, acc3,
-                                                                acc4, acc2b, acc4b, sq, ab, corr, rows, xr);
+            train_pair_packed<PACK, DC, false, TS, NPW, XP, RX, CMP>(a, FP, scr, c, g, xf, xup, ix, acc1, acc2, acc3,
+                                                                     acc4, acc2b, acc4b, sq, ab, corr, rows, xr);
           }
           if (NPW == 2 && pi < npairs) {   // a last lone pair: the oldest of the PS - NPW in flight
             static_assert(NPW == 1 || PS - NPW - 1 >= 0, "ring depth");
@@ -1546,8 +1615,8 @@ __global__ __launch_bounds__(WAVES * 64, OCC) void ae_train_kernel(AEArgs a) {
             float xup[1];
             int ix[1][2];
             load_pair(rs, xf[0], xup[0], ix[0]);
-            train_pair_packed<PACK, DC, false, TS, 1, XP>(a, FP, scr, c, g, xf, xup, ix, acc1, acc2, acc3, acc4, acc2b,
-                                                          acc4b, sq, ab, corr, rows);
+            train_pair_packed<PACK, DC, false, TS, 1, XP, false, CMP>(a, FP, scr, c, g, xf, xup, ix, acc1, acc2, acc3,
+                                                                      acc4, acc2b, acc4b, sq, ab, corr, rows);
           }
           asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // no DMA may land after the ring is retired
         } else {
@@ -1687,7 +1756,7 @@ __global__ __launch_bounds__(WAVES * 64, OCC) void ae_train_kernel(AEArgs a) {
   for (int s = threadIdx.x; s < NSLOT; s += WAVES * 64) {
     if constexpr (ILP == 3) {   // packed accumulators -> parameter-image slots
       int s1, s2;
-      packed_fold_src(s, s1, s2);
+      packed_fold_src<CMP>(s, s1, s2);
       float v = 0.f;
 #pragma unroll
       for (int w = 0; w < WAVES; ++w) {
@@ -2091,7 +2160,7 @@ int ae_train_grid(int64_t n, int max_blocks) {
 hipError_t ae_train_launch(const float* x, int64_t n, int64_t ld, const float* scale, const float* shift,
                            const float* params, float* partials, int64_t* iter, const int64_t* cursor,
                            const int* dims, const int* acts, float l1, int want_acc, int grid, const uint8_t* xpack,
-                           hipStream_t stream, int* grid_used) {
+                           hipStream_t stream, int* grid_used, unsigned xpack_live) {
   AEArgs a{};
   a.x = x; a.n = n; a.ld = ld; a.scale = scale; a.shift = shift; a.params = params;
   a.partials = partials; a.iter = iter; a.cursor = cursor; a.xpack = xpack;
@@ -2137,10 +2206,14 @@ hipError_t ae_train_launch(const float* x, int64_t n, int64_t ld, const float* s
     // A caller that passes a tile-packed ring may have packed it from rows other than x's (an
     // epoch's shuffle fused into the pack: FusedAE.pack_ring); only the XM 1 variants read it,
     // so refuse to silently train on x when none of them applies.
-    const bool xpack_used = xa_ok && ring_ok && D == 18 &&
-                            (train_ilp() == 2 || (((n >> 4) & 1) == 0 && train_ilp() == 3 && dims[1] <= 15 &&
-                                                  dims[2] <= 7 && dims[3] <= 7) || occ == 4);
-    if (xpack != nullptr && !xpack_used && probe < 2) return hipErrorInvalidValue;
+    // xpack_live: the features the packed ring stores (0 = all D).  Only the packed-pair variants
+    // read the compact ring of the cardata live set; any other mask, or any other variant, is refused.
+    const bool pairs_ok = ((n >> 4) & 1) == 0 && train_ilp() == 3 && dims[1] <= 15 && dims[2] <= 7 && dims[3] <= 7;
+    const bool full = xpack_live == 0 || (D <= 31 && xpack_live == (1u << D) - 1u);
+    const bool cm = !full && D == 18 && xpack_live == kLiveCardata;
+    if (xpack != nullptr && !full && !cm) return hipErrorInvalidValue;
+    const bool xpack_used = xa_ok && ring_ok && D == 18 && (cm ? pairs_ok : (train_ilp() == 2 || pairs_ok || occ == 4));
+    if (xpack != nullptr && !xpack_used && (probe < 2 || cm)) return hipErrorInvalidValue;
     if (ring_ok && occ == 4 && D == 18 && want_acc && probe == 2)
       hipLaunchKernelGGL((ae_train_kernel<PACK_REF, true, 3, 4, 18, 2>), gd, bd, 0, stream, a);
     else if (ring_ok && occ == 4 && D == 18 && want_acc && probe == 3)
@@ -2153,7 +2226,22 @@ hipError_t ae_train_launch(const float* x, int64_t n, int64_t ld, const float* s
       const int po = pair_occ();
       pair_grid(po);
       const int xp = pair_xp();
-      if (po == 2)   // two packed pairs per iteration, 2 waves / SIMD
+      if (cm) {   // the compact-ring twin of every variant below
+        if (po == 2)
+          hipLaunchKernelGGL((ae_train_kernel<PACK_REF, true, 8, 2, 18, 1, 3, 10, 2, 0, 1>), gd, bd, 0, stream, a);
+        else if (po == 4 && xp >= 2)
+          hipLaunchKernelGGL((ae_train_kernel<PACK_REF, true, 4, 4, 18, 1, 3, 10, 1, 3, 1>), gd, bd, 0, stream, a);
+        else if (xp == 3)
+          hipLaunchKernelGGL((ae_train_kernel<PACK_REF, true, 6, 3, 18, 1, 3, 10, 1, 3, 1>), gd, bd, 0, stream, a);
+        else if (po == 4)
+          hipLaunchKernelGGL((ae_train_kernel<PACK_REF, true, 4, 4, 18, 1, 3, 10, 1, 1, 1>), gd, bd, 0, stream, a);
+        else if (xp == 1)
+          hipLaunchKernelGGL((ae_train_kernel<PACK_REF, true, 6, 3, 18, 1, 3, 10, 1, 1, 1>), gd, bd, 0, stream, a);
+        else if (xp == 2)
+          hipLaunchKernelGGL((ae_train_kernel<PACK_REF, true, 6, 3, 18, 1, 3, 10, 1, 2, 1>), gd, bd, 0, stream, a);
+        else
+          hipLaunchKernelGGL((ae_train_kernel<PACK_REF, true, 6, 3, 18, 1, 3, 10, 1, 0, 1>), gd, bd, 0, stream, a);
+      } else if (po == 2)   // two packed pairs per iteration, 2 waves / SIMD
         hipLaunchKernelGGL((ae_train_kernel<PACK_REF, true, 8, 2, 18, 1, 3, 10, 2>), gd, bd, 0, stream, a);
       else if (po == 4 && xp >= 2)   // (XP 2 at 4 waves spills: the MFMA-transpose temporaries)
         hipLaunchKernelGGL((ae_train_kernel<PACK_REF, true, 4, 4, 18, 1, 3, 10, 1, 3>), gd, bd, 0, stream, a);

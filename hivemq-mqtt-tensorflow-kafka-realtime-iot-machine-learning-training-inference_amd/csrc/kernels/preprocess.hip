@@ -208,13 +208,30 @@ __device__ __forceinline__ void load_tables(float* s_sc, float* s_sh, int period
 }
 
 // MODE 0: tile-pack (rows + argmax bytes per 16-row tile); MODE 1: argmax bytes only.
+// MODE 2: compact tile-pack.  `live` is a bit mask of the features the tile keeps: per 16-row
+// tile 16 rows x popcount(live) floats, the live features in ascending order, then the same 16
+// argmax bytes (taken over all D normalised values, original feature numbering).  The columns
+// left out are the ones the normaliser assigns a constant 0 (scale = shift = 0, the reference's
+// normalize_fn), and they enter the argmax as that constant, not as raw * 0 + 0: a NaN or Inf
+// in a raw dead column does not reach the pack.
 template <int DT, bool CONTIG, int MODE>
 __global__ __launch_bounds__(kThreads) void rows_group_kernel(const float* __restrict__ x, int64_t n, int64_t ld,
                                                               int Drt, const float* __restrict__ scale,
                                                               const float* __restrict__ shift,
                                                               uint8_t* __restrict__ out, RowSource src,
-                                                              int vec2) {
+                                                              int vec2, uint64_t live) {
   const int D = DT > 0 ? DT : Drt;
+  __shared__ int s_col[64];   // MODE 2: compact column k -> feature
+  const int nlive = MODE == 2 ? __popcll(live) : D;
+  if (MODE == 2 && threadIdx.x < 64) {
+    int k = (int)threadIdx.x, col = 0;
+    for (int f = 0; f < D; ++f)
+      if ((live >> f) & 1) {
+        if (k == 0) col = f;
+        --k;
+      }
+    s_col[threadIdx.x] = col;
+  }
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int period = 4 * D;
   float* s_sc = reinterpret_cast<float*>(smem);
@@ -228,6 +245,8 @@ __global__ __launch_bounds__(kThreads) void rows_group_kernel(const float* __res
   load_tables(s_sc, s_sh, period, D, scale, shift);
   __syncthreads();
   const int tile_chunks = 4 * D;   // float4s of one 16-row tile
+  const int ctile_chunks = 4 * nlive;   // MODE 2: float4s of one compact tile
+  const int out_chunks = MODE == 2 ? ctile_chunks : tile_chunks;
   const int64_t groups = (n + kRowsPerGroup - 1) / kRowsPerGroup;
   for (int64_t g = (int64_t)blockIdx.x * kWaves + wid; g < groups; g += (int64_t)gridDim.x * kWaves) {
     const int64_t r0 = g * kRowsPerGroup;
@@ -240,20 +259,39 @@ __global__ __launch_bounds__(kThreads) void rows_group_kernel(const float* __res
     for (int h = 0; h < 2; ++h) {
       const int r = lane + 64 * h;
       if (r < nrows) {
+        if (MODE == 2) {   // dead columns: the constant 0 (this lane's own row, in LDS order)
+          for (int f = 0; f < D; ++f)
+            if (!((live >> f) & 1)) stage[r * D + f] = 0.f;
+        }
         const int a = argmax_row<DT>(stage + r * D, D);
-        if (MODE == 0)
+        if (MODE != 1)
           s_arg[r] = (uint8_t)a;
         else
           out[r0 + r] = (uint8_t)a;   // 64 consecutive bytes per instruction
       }
     }
-    if (MODE == 0) {
+    if (MODE == 0 || MODE == 2) {
       wave_lds_sync();
       const int ntiles = nrows >> 4;
       if (lane < ntiles) {
         const int64_t t = (r0 >> 4) + lane;
-        *reinterpret_cast<uint4*>(out + (t * (tile_chunks + 1) + tile_chunks) * 16) =
+        *reinterpret_cast<uint4*>(out + (t * (out_chunks + 1) + out_chunks) * 16) =
             *reinterpret_cast<const uint4*>(s_arg + 16 * lane);
+      }
+    }
+    if (MODE == 2) {   // the live columns of the staged rows, one float4 of the compact tile per lane
+      const int nvec = (nrows * nlive) >> 2;   // nrows is a multiple of 16
+      float* ostream = reinterpret_cast<float*>(out) + 4 * (r0 >> 4) * (int64_t)(ctile_chunks + 1);
+      for (int c = lane; c < nvec; c += 64) {
+        const int t = c / ctile_chunks, w = c - t * ctile_chunks;
+        float v[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const int e = 4 * c + q, r = e / nlive, k = e - r * nlive;
+          v[q] = stage[r * D + s_col[k]];
+        }
+        *reinterpret_cast<float4*>(ostream + 4 * ((int64_t)t * (ctile_chunks + 1) + w)) =
+            make_float4(v[0], v[1], v[2], v[3]);
       }
     }
     wave_lds_sync();   // the stage is rewritten by the next group
@@ -272,7 +310,8 @@ int stream_grid(int64_t groups_of_waves) {
 
 template <int MODE>
 hipError_t launch_rows_group(const float* x, int64_t n, int64_t ld, int D, const float* scale, const float* shift,
-                             uint8_t* out, hipStream_t stream, RowSource src = RowSource{nullptr, 0, 0, 0}) {
+                             uint8_t* out, hipStream_t stream, RowSource src = RowSource{nullptr, 0, 0, 0},
+                             uint64_t live = 0) {
   const bool gather = src.index != nullptr || src.half > 0;
   const bool contig = !gather && ld == D && (reinterpret_cast<uintptr_t>(x) & 15) == 0;
   const int vec2 = (ld & 1) == 0 && (reinterpret_cast<uintptr_t>(x) & 7) == 0;
@@ -298,16 +337,16 @@ hipError_t launch_rows_group(const float* x, int64_t n, int64_t ld, int D, const
   }
   if (D == 18 && contig)
     hipLaunchKernelGGL((rows_group_kernel<18, true, MODE>), grid, block, lds, stream, x, n, ld, D, scale, shift, out,
-                       src, vec2);
+                       src, vec2, live);
   else if (contig)
     hipLaunchKernelGGL((rows_group_kernel<0, true, MODE>), grid, block, lds, stream, x, n, ld, D, scale, shift, out,
-                       src, vec2);
+                       src, vec2, live);
   else if (D == 18)
     hipLaunchKernelGGL((rows_group_kernel<18, false, MODE>), grid, block, lds, stream, x, n, ld, D, scale, shift, out,
-                       src, vec2);
+                       src, vec2, live);
   else
     hipLaunchKernelGGL((rows_group_kernel<0, false, MODE>), grid, block, lds, stream, x, n, ld, D, scale, shift, out,
-                       src, vec2);
+                       src, vec2, live);
   return hipGetLastError();
 }
 
@@ -470,12 +509,16 @@ hipError_t normalize_filter_launch(const float* x, int64_t n, int64_t ld, int D,
 
 hipError_t pack_tiles_argmax_launch(const float* x, int64_t n, int64_t ld, int D, const float* scale,
                                     const float* shift, uint8_t* out, hipStream_t stream, const int64_t* index,
-                                    uint64_t perm_key, int64_t perm_n) {
+                                    uint64_t perm_key, int64_t perm_n, uint64_t live_mask) {
   if (n <= 0) return hipSuccess;
   if ((n & 15) || D < 1 || D > 64) return hipErrorInvalidValue;
   if (reinterpret_cast<uintptr_t>(out) & 15) return hipErrorInvalidValue;
   if (perm_n > 0 && (index != nullptr || n > perm_n)) return hipErrorInvalidValue;
   const RowSource src{index, perm_key, perm_n, perm_n > 0 ? perm_half_bits(perm_n) : 0};
+  const uint64_t all = D == 64 ? ~0ull : (1ull << D) - 1ull;
+  if (live_mask & ~all) return hipErrorInvalidValue;
+  if (live_mask != 0 && live_mask != all)   // compact tiles: the live features only
+    return launch_rows_group<2>(x, n, ld, D, scale, shift, out, stream, src, live_mask);
   return launch_rows_group<0>(x, n, ld, D, scale, shift, out, stream, src);
 }
 

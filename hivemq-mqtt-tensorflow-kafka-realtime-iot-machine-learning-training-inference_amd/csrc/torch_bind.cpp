@@ -71,7 +71,8 @@ int64_t ae_train_partials(const at::Tensor& x, const c10::optional<at::Tensor>& 
                           const c10::optional<at::Tensor>& shift, const at::Tensor& params, at::Tensor& partials,
                           const c10::optional<at::Tensor>& iter, std::vector<int64_t> dims, std::vector<int64_t> acts,
                           double l1, bool want_acc, int64_t max_blocks, int64_t n_rows,
-                          const c10::optional<at::Tensor>& cursor, const c10::optional<at::Tensor>& xpack) {
+                          const c10::optional<at::Tensor>& cursor, const c10::optional<at::Tensor>& xpack,
+                          int64_t xpack_live) {
   check_ae_dims(dims, acts);
   check_dev(x, "x", at::kFloat);
   TORCH_CHECK(x.dim() == 2 && x.stride(1) == 1, "x must be [n, ld] with unit column stride");
@@ -102,10 +103,15 @@ int64_t ae_train_partials(const at::Tensor& x, const c10::optional<at::Tensor>& 
   }
   const uint8_t* xpack_ptr = nullptr;
   if (xpack.has_value() && xpack->defined()) {
+    // xpack_live (0: all D features): the live mask the ring was packed with; its size follows
+    TORCH_CHECK(xpack_live >= 0 && xpack_live < (int64_t(1) << dims[0]), "xpack_live: a mask of the D features");
+    const int64_t cols = xpack_live ? __builtin_popcountll((unsigned long long)xpack_live) : dims[0];
     TORCH_CHECK(xpack->is_cuda() && xpack->scalar_type() == at::kByte && xpack->is_contiguous() &&
-                    x.size(0) % 16 == 0 && xpack->numel() == x.size(0) / 16 * (64 * dims[0] + 16),
-                "xpack must be the tile-packed ring of x (pack_tiles_argmax)");
+                    x.size(0) % 16 == 0 && xpack->numel() == x.size(0) / 16 * (64 * cols + 16),
+                "xpack must be the tile-packed ring of x (pack_tiles_argmax with the same live mask)");
     xpack_ptr = xpack->data_ptr<uint8_t>();
+  } else {
+    TORCH_CHECK(xpack_live == 0, "xpack_live without xpack");
   }
   const int grid = sml::ae_train_grid(n, (int)max_blocks);
   TORCH_CHECK(partials.numel() >= (int64_t)grid * sml::ae_nslot(), "partials buffer too small for grid ", grid);
@@ -116,7 +122,7 @@ int64_t ae_train_partials(const at::Tensor& x, const c10::optional<at::Tensor>& 
   SML_CHECK_HIP(sml::ae_train_launch(x.data_ptr<float>(), n, x.stride(0), opt_ptr(scale), opt_ptr(shift),
                                      params.data_ptr<float>(), partials.data_ptr<float>(), iter_ptr, cur_ptr, d, a,
                                      (float)l1,
-                                     want_acc ? 1 : 0, grid, xpack_ptr, cur_stream(x), &used));
+                                     want_acc ? 1 : 0, grid, xpack_ptr, cur_stream(x), &used, (unsigned)xpack_live));
   return used;
 }
 
@@ -125,10 +131,14 @@ int64_t ae_train_partials(const at::Tensor& x, const c10::optional<at::Tensor>& 
 // existing byte buffer of at least the packed size (e.g. a slice of a ring being refilled)
 // perm_n > 0: pack rows x[perm_row(r, perm_n, perm_key)] for r < n_rows (default perm_n): an
 // epoch's shuffle as a keyed bijection evaluated in the kernel
+// live_mask (0 = all D): the compact layout, 16 rows x popcount(live_mask) floats + the same 16
+// argmax bytes per tile.  The features left out are the ones the normaliser zeroes: they are
+// taken as the constant 0 (not raw * 0 + 0), so a NaN / Inf in a raw dead column does not poison
+// the row -- as in the reference, whose normalize_fn assigns a constant.
 at::Tensor pack_tiles_argmax(const at::Tensor& x, int64_t D, const c10::optional<at::Tensor>& scale,
                              const c10::optional<at::Tensor>& shift, const c10::optional<at::Tensor>& index,
                              const c10::optional<at::Tensor>& out_opt, uint64_t perm_key, int64_t perm_n,
-                             int64_t n_rows) {
+                             int64_t n_rows, uint64_t live_mask) {
   check_dev(x, "x", at::kFloat);
   TORCH_CHECK(x.dim() == 2 && x.stride(1) == 1 && x.size(1) >= D && D >= 1 && D <= 64,
               "x must be [n, >=D] with D <= 64");
@@ -158,7 +168,10 @@ at::Tensor pack_tiles_argmax(const at::Tensor& x, int64_t D, const c10::optional
     n = n_rows;
   }
   TORCH_CHECK(n % 16 == 0, "packed rows must be a multiple of 16");
-  const int64_t bytes = n / 16 * (64 * D + 16);
+  const uint64_t all = D == 64 ? ~0ull : (1ull << D) - 1ull;
+  TORCH_CHECK((live_mask & ~all) == 0, "live_mask has bits past D");
+  const int64_t cols = live_mask ? __builtin_popcountll(live_mask) : D;
+  const int64_t bytes = n / 16 * (64 * cols + 16);
   c10::hip::HIPGuard guard(x.device().index());
   at::Tensor out;
   if (out_opt.has_value() && out_opt->defined()) {
@@ -171,7 +184,7 @@ at::Tensor pack_tiles_argmax(const at::Tensor& x, int64_t D, const c10::optional
   }
   SML_CHECK_HIP(sml::pack_tiles_argmax_launch(x.data_ptr<float>(), n, x.stride(0), (int)D, opt_ptr(scale),
                                               opt_ptr(shift), out.data_ptr<uint8_t>(), cur_stream(x), idx, perm_key,
-                                              perm_n));
+                                              perm_n, live_mask));
   return out;
 }
 
@@ -1449,11 +1462,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("ae_train_partials", &ae_train_partials, "fused AE fwd+bwd -> per-workgroup gradient slabs",
         py::arg("x"), py::arg("scale"), py::arg("shift"), py::arg("params"), py::arg("partials"), py::arg("iter"),
         py::arg("dims"), py::arg("acts"), py::arg("l1"), py::arg("want_acc"), py::arg("max_blocks"),
-        py::arg("n_rows") = -1, py::arg("cursor") = py::none(), py::arg("xpack") = py::none());
+        py::arg("n_rows") = -1, py::arg("cursor") = py::none(), py::arg("xpack") = py::none(),
+        py::arg("xpack_live") = 0);
   m.def("pack_tiles_argmax", &pack_tiles_argmax, "tile-packed training ring (rows + ingest-time argmax per tile)",
         py::arg("x"), py::arg("D"), py::arg("scale") = py::none(), py::arg("shift") = py::none(),
         py::arg("index") = py::none(), py::arg("out") = py::none(), py::arg("perm_key") = 0,
-        py::arg("perm_n") = 0, py::arg("n_rows") = -1);
+        py::arg("perm_n") = 0, py::arg("n_rows") = -1, py::arg("live_mask") = 0);
   m.def("perm_indices", &perm_indices, "the pack's keyed row bijection of [0, n), materialised", py::arg("like"),
         py::arg("n"), py::arg("key"), py::arg("start") = 0, py::arg("count") = -1);
   m.def("row_argmax_u8", &row_argmax_u8, "ingest-time argmax of each normalised row (uint8)", py::arg("x"),

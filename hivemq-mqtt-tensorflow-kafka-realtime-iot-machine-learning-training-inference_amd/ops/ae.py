@@ -141,6 +141,7 @@ class FusedAE:
         self.cursor = torch.zeros(1, dtype=torch.int64, device=dev)
         self.ring: Optional[torch.Tensor] = None
         self.ring_xpack: Optional[torch.Tensor] = None
+        self.ring_live = 0      # live-feature mask of a compact ring_xpack (0: all columns)
         self.ring_batch = 0
         self.set_normalizer(scale, shift)
 
@@ -148,9 +149,13 @@ class FusedAE:
     def set_normalizer(self, scale: Optional[np.ndarray], shift: Optional[np.ndarray]) -> None:
         if scale is None:
             self.scale = self.shift = None
+            self._norm_live = 0
         else:
-            self.scale = torch.as_tensor(np.asarray(scale, dtype=np.float32), device=self.device)
-            self.shift = torch.as_tensor(np.asarray(shift, dtype=np.float32), device=self.device)
+            sc, sh = np.asarray(scale, dtype=np.float32), np.asarray(shift, dtype=np.float32)
+            self.scale = torch.as_tensor(sc, device=self.device)
+            self.shift = torch.as_tensor(sh, device=self.device)
+            # bit f set: feature f is live (the normaliser does not assign it the constant 0)
+            self._norm_live = sum(1 << f for f in range(min(len(sc), len(sh), self.spec.input_dim)) if sc[f] != 0 or sh[f] != 0)
 
     # -- state -------------------------------------------------------------------------
     def get_weights(self) -> List[np.ndarray]:
@@ -210,8 +215,28 @@ class FusedAE:
         # gets x's half of the accuracy metric with the tile's own two DMAs and skips the
         # 8-feature x 4-lane argmax of x per tile (profiles/r02/SUMMARY.md).
         self.ring_xpack = None
+        self.ring_live = 0
         if self._xpack_ok(ring.size(0), batch) and ring.size(1) == self.spec.input_dim:
-            self.ring_xpack = self.C.pack_tiles_argmax(ring, self.spec.input_dim, self.scale, self.shift)
+            self.ring_live = self._compact_mask(batch)
+            self.ring_xpack = self.C.pack_tiles_argmax(ring, self.spec.input_dim, self.scale, self.shift,
+                                                       live_mask=self.ring_live)
+
+    # The features the reference's normalize_fn keeps (cardata NORMALIZE_RANGES is None for
+    # coolant_temp, intake_air_flow_speed, battery_voltage and current_draw: indices 0, 2, 4, 5).
+    COMPACT_LIVE = 0x3FFFF & ~((1 << 0) | (1 << 2) | (1 << 4) | (1 << 5))
+
+    def _compact_mask(self, batch: int) -> int:
+        """Live-feature mask of the compact packed ring, or 0 for the 18-column layout.  The
+        compact ring (14 floats per row: the columns the normaliser zeroes are left out) is read
+        by the packed-pair kernel only: an even tile count per batch, ``SML_AE_ILP`` unset or 3,
+        hidden layers <= 7 wide, and a normaliser whose dead set (scale == shift == 0) is exactly
+        cardata's.  ``SML_AE_COMPACT=0`` keeps the 18-column layout (A/B; read when the ring is
+        attached, like ``SML_AE_XPACK``)."""
+        if os.environ.get("SML_AE_COMPACT", "1") == "0" or os.environ.get("SML_AE_ILP", "3")[:1] in ("1", "2"):
+            return 0
+        if (batch // 16) % 2 or self.spec.encoding_dim > 15 or self.spec.hidden_dim > 7:
+            return 0
+        return self._norm_live if self._norm_live == self.COMPACT_LIVE else 0
 
     def _xpack_ok(self, rows: int, batch: int) -> bool:
         """The tile-packed ring applies: the reference model (D = 18, reference activations,
@@ -242,21 +267,24 @@ class FusedAE:
             src = x[index[:rows]] if index is not None else x[:rows]
             self.attach_ring(src.contiguous(), B)
             return rows
-        nbytes = rows // 16 * (64 * self.spec.input_dim + 16)
+        live = self._compact_mask(B)
+        nbytes = rows // 16 * (64 * (bin(live).count("1") if live else self.spec.input_dim) + 16)
         buf = getattr(self, "_pack_buf", None)
         if not reuse or buf is None or buf.numel() < nbytes:
             buf = self._pack_buf = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
         if perm_key is not None:
             self.C.pack_tiles_argmax(x, self.spec.input_dim, self.scale, self.shift, None, buf,
-                                     perm_key=int(perm_key) & ((1 << 64) - 1), perm_n=int(x.size(0)), n_rows=rows)
+                                     perm_key=int(perm_key) & ((1 << 64) - 1), perm_n=int(x.size(0)), n_rows=rows,
+                                     live_mask=live)
         else:
             idx = index[:rows].contiguous() if index is not None else None
             self.C.pack_tiles_argmax(x if idx is not None else x[:rows], self.spec.input_dim, self.scale, self.shift,
-                                     idx, buf)
+                                     idx, buf, live_mask=live)
         # the ring tensor only carries the geometry (rows, stride): with a packed ring the
         # launcher reads the rows from the pack alone and refuses any variant that would not
         self.ring, self.ring_batch = x[:rows], B
         self.ring_xpack = buf[:nbytes]
+        self.ring_live = live
         self.cursor.zero_()
         return rows
 
@@ -273,7 +301,8 @@ class FusedAE:
         gb = B if global_batch is None else int(global_batch)
         G = self.C.ae_train_partials(self.ring, self.scale, self.shift, self.params, self.partials, self.iter,
                                      self.spec.dims, self.spec.act_codes, float(self.spec.activity_l1),
-                                     bool(self.want_acc), self.max_blocks, B, self.cursor, self.ring_xpack)
+                                     bool(self.want_acc), self.max_blocks, B, self.cursor, self.ring_xpack,
+                                     xpack_live=self.ring_live if self.ring_xpack is not None else 0)
         if allreduce is None:
             self.reduce(G, RA_ADAM | RA_METRICS | RA_ADVANCE, gscale=1.0 / gb)
         else:
