@@ -172,11 +172,16 @@ bool lstm_fused_frag_supported(int U, int IN, bool x_bf16, bool want_dx);
 hipError_t pack_tiles_argmax_launch(const float* x, int64_t n, int64_t ld, int D, const float* scale,
                                     const float* shift, uint8_t* out, hipStream_t stream,
                                     const int64_t* index = nullptr, uint64_t perm_key = 0, int64_t perm_n = 0,
-                                    uint64_t live_mask = 0);
+                                    uint64_t live_mask = 0, bool lane_order = false);
 // live_mask (0 or all D bits: the layout above): the compact layout -- per tile 16 rows x
 // popcount(live_mask) floats, the live features in ascending order, then the same 16 argmax
 // bytes (over all D values, original numbering); n/16 * (64*popcount + 16) bytes.  The features
 // left out must be the ones the normaliser zeroes; they count as the constant 0 in the argmax.
+// lane_order (D = 18 and the cardata live set only, anything else is refused): the 14 floats of
+// a row in the order the packed-pair train loop's lanes read them -- features 16, 1, 17, 3, 6,
+// 7, ..., 15.  This is the only compact layout ae_train_launch reads (xpack_live = the cardata
+// live set means a ring packed with lane_order); no kernel reads the ascending compact layout,
+// which stays the default of the pack for callers that want the plain live columns.
 // out[i] = perm_row(start + i, n, key): the same bijection, materialised (short batches, tests)
 hipError_t perm_indices_launch(int64_t* out, int64_t start, int64_t count, int64_t n, uint64_t key,
                                hipStream_t stream);

@@ -31,7 +31,9 @@
 //  * the cardata normaliser zeroes four of the 18 features, so its packed ring stores the 14
 //    live ones (compact ring, CM variants of the packed-pair loop): 57 instead of 73 B per
 //    row from HBM and through LDS.  The compute is the 18-column loop's, operand for operand,
-//    so the results are bit-identical to it (profiles/r07/compact_ring).
+//    so the results are bit-identical to it (profiles/r07/compact_ring).  A compact row holds
+//    its features in the order the loop's lanes read them (16, 1, 17, 3, 6, 7, ..., 15), so
+//    every live input lands in its operand slot with no select (profiles/r08/loop_diet).
 //
 // Padded parameter image (fp32, 1536 floats), row-major [in][out]:
 //   L1 [32][16] @0    (bias = row 31)     requires D  <= 31, n1 <= 15
@@ -839,15 +841,15 @@ __device__ __forceinline__ void train_tiles_ilp(const AEArgs& a, const Frags& F,
 //   The accumulators hold both tiles' halves side by side and are folded into the parameter
 //   image once per launch (packed_fold_src).  Needs n2, n3 <= 7.
 //
-// Compact ring (CM, pack_tiles_argmax with a live mask): the reference's normalize_fn assigns
-// the constant 0 to features 0, 2, 4 and 5 (cardata NORMALIZE_RANGES None), so the packed ring
-// stores only the 14 live ones, in ascending feature order (compact float k: feature 1, 3, 6,
-// 7, ..., 17).  The loop keeps the 18-column operand layout -- lane (c, g) holds inputs
-// 4g..4g+3 of row c, inputs 16 / 17 come as UP -- and only reads them from other places:
-//   g = 0: inputs (0, 1, 2, 3)   <- (*, k0, *, k1)      g = 2: inputs 8..11  <- k4..k7
-//   g = 1: inputs (4, 5, 6, 7)   <- (*, *, k2, k3)      g = 3: inputs 12..15 <- k8..k11
-// as four consecutive floats of the row from ONE lane offset (cm_off), g = 0 moving its k0 / k1
-// into place with two selects.  A dead slot `*` holds whatever float of the same row came along
+// Compact ring (CM, pack_tiles_argmax with a live mask and lane_order): the reference's
+// normalize_fn assigns the constant 0 to features 0, 2, 4 and 5 (cardata NORMALIZE_RANGES None),
+// so the packed ring stores only the 14 live ones, in LANE order (compact float k: feature 16, 1,
+// 17, 3, 6, 7, ..., 15).  The loop keeps the 18-column operand layout -- lane (c, g) holds inputs
+// 4g..4g+3 of row c, inputs 16 / 17 come as UP -- and reads them as four consecutive floats of
+// the row from ONE lane offset (cm_off: byte 0, 8, 24, 40), every live input already in its slot:
+//   g = 0: inputs (0, 1, 2, 3)   <- k0..k3 = (*16, 1, *17, 3)     g = 2: inputs 8..11  <- k6..k9
+//   g = 1: inputs (4, 5, 6, 7)   <- k2..k5 = (*17, *3, 6, 7)      g = 3: inputs 12..15 <- k10..k13
+// and UP from k0 / k2.  A dead slot `*` holds whatever float of the same row came along
 // (always landed, always finite -- nothing outside the row is read): its layer-1
 // weight row is zeroed in the fragment (the 18-column loop multiplies a zero input by the
 // weight, this one a finite input by zero: both products are 0), its dW1 row is written as the
@@ -855,19 +857,23 @@ __device__ __forceinline__ void train_tiles_ilp(const AEArgs& a, const Frags& F,
 // the same instruction on the same operands, so the results are the 18-column loop's.
 constexpr unsigned kLiveCardata = 0x3FFFFu & ~((1u << 0) | (1u << 2) | (1u << 4) | (1u << 5));
 __host__ __device__ constexpr bool cm_dead(int f) { return f == 0 || f == 2 || f == 4 || f == 5; }
-// byte offset, from the row's first compact float, of the lane's four floats: g = 0 and g = 1
-// read k0..k3, g = 2 k4..k7, g = 3 k8..k11
-__device__ __forceinline__ int cm_off(int g) { return g < 2 ? 0 : g == 2 ? 16 : 32; }
-// the lane's inputs 4g..4g+3 of one compact row (dead slots: finite don't-cares)
-__device__ __forceinline__ f32x4 cm_row_x(const char* row, int g) {
+// byte offset, from the row's first compact float, of the lane's four floats: {0, 8, 24, 40} for
+// g = 0..3.  Branch-free on purpose: a nested ?: over g became exec-masked branches inside the loop.
+__device__ __forceinline__ int cm_off(int g) { return max(16 * g - 8, 0); }
+// the lane's inputs 4g..4g+3 of one compact row (dead slots: finite don't-cares): the four
+// consecutive floats at `lane_row` = the row's first float + cm_off(g), no select
+typedef __attribute__((address_space(3))) const char lds_cc;
+__device__ __forceinline__ f32x4 ring_row4(lds_cc* lane_row) {   // one ds_read2_b64
   typedef __attribute__((address_space(3))) const f32x2_t lds_f2;
-  const f32x2_t a = *(lds_f2*)(row + cm_off(g)), b = *(lds_f2*)(row + cm_off(g) + 8);
-  return f32x4{a[0], g == 0 ? a[0] : a[1], b[0], g == 0 ? a[1] : b[1]};   // g = 0: inputs 1 / 3 are k0 / k1
+  const f32x2_t a = *(lds_f2*)lane_row, b = *(lds_f2*)(lane_row + 8);
+  return f32x4{a[0], a[1], b[0], b[1]};
 }
-// the same with the dead inputs as the constant 0 they are (the loss's targets)
-__device__ __forceinline__ f32x4 cm_zero_dead(f32x4 x, int g) {
-  return f32x4{g < 2 ? 0.f : x[0], g == 1 ? 0.f : x[1], g == 0 ? 0.f : x[2], x[3]};
-}
+__device__ __forceinline__ f32x4 cm_row_x(const char* lane_row) { return ring_row4((lds_cc*)lane_row); }
+
+template <int V>
+struct RingSlot {   // a ring slot as a compile-time value (the unrolled pair loop)
+  static constexpr int value = V;
+};
 
 struct FragsP {
   bf16x4 w1t;         // L1 forward from inputs 0..15 (prescaled)
@@ -1059,16 +1065,22 @@ __device__ __forceinline__ bf16x4 tr_read(char* slot, int c, int g) {
 // stalls waiting to issue LDS instructions (SQ_WAIT_INST_LDS, profiles/r06/SUMMARY.md §1).
 // RX (tile-packed ring only): the fp32 inputs the loss needs (y - x) are read again from the pair's
 // ring slot at the output layer instead of being held in 9 registers across the whole forward
-// chain (`xring[p]`: the pair's slot base; the slot is only re-filled after the next iteration's DMA
-// issue).  The ring's rows are the normalised ones, bit-identical to the first read.
+// chain (`xrow[p]` / `xupa[p]`: the LDS addresses this lane read its four inputs of the pair's first
+// tile and its UP input from; the slot is only re-filled after the next iteration's DMA issue).
+// The ring's rows are the normalised ones, bit-identical to the first read.
 // CM (compact ring): xf's dead-input slots are don't-cares (see cm_row_x); the RX re-read takes
 // the compact offsets and the loss masks the dead slots' targets to 0.
-template <int PACK, int DC, bool TP, int TS = 10, int NP = 1, int XP = 0, bool RX = false, bool CM = false>
+// WA: the variant is only ever launched with want_acc (the tile-packed ring variants, XM 1), so the
+// metric block is unconditional: no branch, and the argmax of y fills the backward chain's MFMA waits.
+// RC: count the rows here (false: the caller sets them from its trip count after the loop).
+template <int PACK, int DC, bool TP, int TS = 10, int NP = 1, int XP = 0, bool RX = false, bool CM = false,
+          bool WA = false, bool RC = true>
 __device__ __forceinline__ void train_pair_packed(const AEArgs& a, const FragsP& F, char* scr, int c, int g,
                                                   const f32x4 (&xf)[NP][2][2], const float (&xup)[NP],
                                                   const int (&ix)[NP][2], f32x4 acc1[2], f32x4& acc2, f32x4& acc3,
                                                   f32x4 acc4[2], f32x4& acc2b, f32x4& acc4b, float& sq, float& ab,
-                                                  float& corr, float& rows, const char* const* xring = nullptr) {
+                                                  float& corr, float& rows, lds_cc* const* xrow = nullptr,
+                                                  lds_cc* const* xupa = nullptr) {
   // xup: the UP-layout copy of inputs 16 / 17 (lane group g: input 16 + (g & 1) of tile g >> 1)
   static_assert(PACK == PACK_REF && DC == 18, "reference model, D = 18 (outputs 16, 17 packed as UP)");
   static_assert(NP == 1 || NP == 2, "one or two pairs per iteration");
@@ -1102,8 +1114,15 @@ __device__ __forceinline__ void train_pair_packed(const AEArgs& a, const FragsP&
 #pragma unroll
   for (int p = 0; p < NP; ++p) {
     if constexpr (MA) {   // the shared A operand; tile u's UP lanes (g >> 1 == u) + the bias lane
-      const bf16x4 xu0 = pack4(f32x4{g < 2 ? xup[p] : 0.f, g == 0 ? 1.0f : 0.0f, 0.f, 0.f});
-      const bf16x4 xu1 = pack4(f32x4{g >= 2 ? xup[p] : 0.f, g == 0 ? 1.0f : 0.0f, 0.f, 0.f});
+      // (xup of tile u's lanes | the bias one) without converting again: the low word of xub is
+      // (bf16(xup), bf16 one-or-zero), so xu0 is xub with lane groups 2 / 3 zeroed, and xu1 is xub in
+      // lane groups 2 / 3 (whose bias half is 0) and the lane-invariant (0, one-or-zero) elsewhere --
+      // the fp32 bits of 1.0 / 0.0 are that packed word.  The same bf16 bits as two more pack4s.
+      typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+      const unsigned xw = __builtin_bit_cast(u32x2, xub[p])[0];
+      const unsigned bias_w = __float_as_uint(g == 0 ? 1.0f : 0.0f);
+      const bf16x4 xu0 = __builtin_bit_cast(bf16x4, u32x2{g < 2 ? xw : 0u, 0u});
+      const bf16x4 xu1 = __builtin_bit_cast(bf16x4, u32x2{g >= 2 ? xw : bias_w, 0u});
       z1[p][0] = mfma32a(F.w1s, xb0[p][0], xu0, zero4);
       z1[p][1] = mfma32a(F.w1s, xb0[p][1], xu1, zero4);
     } else {
@@ -1161,30 +1180,22 @@ __device__ __forceinline__ void train_pair_packed(const AEArgs& a, const FragsP&
 #pragma unroll
   for (int p = 0; p < NP; ++p) {
     if constexpr (RX) {
-      typedef __attribute__((address_space(3))) const f32x2_t lds_f2;
       typedef __attribute__((address_space(3))) const float lds_f;
       constexpr int DR = CM ? 14 : 18, SLOTB = 64 * DR + 16;
 #pragma unroll
-      for (int u = 0; u < 2; ++u) {
-        if constexpr (CM) {
-          xl[p][u] = cm_row_x(xring[p] + u * SLOTB + c * 4 * DR, g);
-        } else {
-          const char* row = xring[p] + u * SLOTB + c * 4 * 18 + 16 * g;
-          const f32x2_t v0 = *(lds_f2*)row, v1 = *(lds_f2*)(row + 8);
-          xl[p][u] = f32x4{v0[0], v0[1], v1[0], v1[1]};
-        }
-      }
-      xul[p] = *(lds_f*)(xring[p] + c * 4 * DR + 4 * (DR - 2 + (g & 1)) + (g >= 2 ? SLOTB : 0));
+      for (int u = 0; u < 2; ++u) xl[p][u] = ring_row4(xrow[p] + u * SLOTB);
+      xul[p] = *(lds_f*)xupa[p];
     } else {
 #pragma unroll
       for (int u = 0; u < 2; ++u) xl[p][u] = xf[p][u][0];
       xul[p] = xup[p];
     }
-    if constexpr (CM) {
-#pragma unroll
-      for (int u = 0; u < 2; ++u) xl[p][u] = cm_zero_dead(xl[p][u], g);
-    }
   }
+  // CM: the dead slots' targets are 0.  e = fma(-x, m, y) with the lane-invariant mask m (1 live,
+  // 0 dead; slot 3 is always live) instead of a select per target: m = 1 is y - x with its one
+  // rounding, m = 0 leaves y (x is finite, and where y is a zero of either sign the loss and the
+  // relu derivative below do not see the sign of e).
+  const float cm_m[3] = {g < 2 ? 0.f : 1.f, g == 1 ? 0.f : 1.f, g == 0 ? 0.f : 1.f};
 #pragma unroll
   for (int p = 0; p < NP; ++p) {
 #pragma unroll
@@ -1198,7 +1209,7 @@ __device__ __forceinline__ void train_pair_packed(const AEArgs& a, const FragsP&
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         y[p][u][i] = relu_fast(z4[p][u][i]);
-        float e = y[p][u][i] - xl[p][u][i];
+        float e = (CM && i < 3) ? fmaf(-xl[p][u][i], cm_m[i], y[p][u][i]) : y[p][u][i] - xl[p][u][i];
         if (stand_in(p, u)) e = 0.f;
         sq = fmaf(e, e, sq);
         dz4[p][u][i] = y[p][u][i] > 0.f ? e : 0.f;   // relu'; x 2/D folded into F.w4b / the acc4 slab
@@ -1209,7 +1220,7 @@ __device__ __forceinline__ void train_pair_packed(const AEArgs& a, const FragsP&
     sq = fmaf(eup, eup, sq);
     dz4up[p] = yup[p] > 0.f ? eup : 0.f;
   }
-  if (a.want_acc) {   // lane group 0 counts row c of tile 0, group 1 row c of tile 1
+  if (WA || a.want_acc) {   // lane group 0 counts row c of tile 0, group 1 row c of tile 1
 #pragma unroll
     for (int p = 0; p < NP; ++p) {
       const int iy = row_argmax_up_pair(y[p][0], y[p][1], yup[p], g);
@@ -1218,7 +1229,7 @@ __device__ __forceinline__ void train_pair_packed(const AEArgs& a, const FragsP&
       corr += (((TP && p == NP - 1) ? g == 0 : g < 2) && iy == ixs) ? 1.f : 0.f;
     }
   }
-  rows += (g == 0) ? (TP ? 2.f * NP - 1.f : 2.f * NP) : 0.f;
+  if constexpr (RC) rows += (g == 0) ? (TP ? 2.f * NP - 1.f : 2.f * NP) : 0.f;
 
   bf16x4 dz4b[NP][2], dz1b[NP][2], dz4bu[NP], dz3b[NP], dz2b[NP];
   f32x4 d3[NP], d2[NP];
@@ -1503,7 +1514,7 @@ __global__ __launch_bounds__(WAVES * 64, OCC) void ae_train_kernel(AEArgs a) {
           typedef __attribute__((address_space(3))) const unsigned char lds_u8;
           if constexpr (XM == 1) ix = (int)*(lds_u8*)(ring + slot * slotb + (slotb - 16) + c);
           if constexpr (CMP) {   // the same inputs 0..15 from the compact row
-            xf[0] = cm_row_x(ring + slot * slotb + c * 4 * DR, g);
+            xf[0] = cm_row_x(ring + slot * slotb + c * 4 * DR + cm_off(g));
             xf[1] = f32x4{0.f, 0.f, 0.f, 0.f};
             return;
           }
@@ -1524,7 +1535,8 @@ __global__ __launch_bounds__(WAVES * 64, OCC) void ae_train_kernel(AEArgs a) {
         // tile 1 of a pair sits in the next slot (pairs start on even slots, PF even), so one
         // loop-invariant lane offset covers both tiles
         static_assert(ILP != 3 || PF % 2 == 0, "pairs start on even ring slots");
-        const int up_off = c * 4 * DR + 4 * (DR - 2 + (g & 1)) + (g >= 2 ? slotb : 0);   // CM: compact floats 12 / 13
+        const int row_off = c * 4 * DR + (CMP ? cm_off(g) : 16 * g);   // the lane's inputs 4g..4g+3 (packed pairs)
+        const int up_off = c * 4 * DR + (CMP ? 8 * (g & 1) : 4 * (DR - 2 + (g & 1))) + (g >= 2 ? slotb : 0);   // CM: compact floats 0 / 2
         auto ring_up = [&](int slot) -> float {   // slot: the pair's first tile
           typedef __attribute__((address_space(3))) const float lds_f;
           return *(lds_f*)(ring + slot * slotb + up_off);
@@ -1539,8 +1551,7 @@ __global__ __launch_bounds__(WAVES * 64, OCC) void ae_train_kernel(AEArgs a) {
           const int pairb = 2 * slotb;
           const int nl3 = (pairb - (CMP ? 1024 : 2048)) >> 4;   // lanes of the last DMA
           const int64_t npairs = nfull >> 1;
-          auto issue_pair = [&](int64_t pi, int ps) {
-            pi = pi < npairs ? pi : npairs - 1;   // prefetch past the end re-reads the last pair
+          auto issue_pair_at = [&](int64_t pi, int ps) {   // pi < npairs
             // XM 1: the tile-packed ring; XM 0: the raw rows themselves (ld == D: a pair of
             // whole tiles is 32 contiguous rows = pairb bytes)
             const char* src = (XM == 1 ? reinterpret_cast<const char*>(a.xpack) : reinterpret_cast<const char*>(a.x)) +
@@ -1554,6 +1565,10 @@ __global__ __launch_bounds__(WAVES * 64, OCC) void ae_train_kernel(AEArgs a) {
               if (lane < nl3) glds16(src + 2048, voff, dst + 2048);
             }
           };
+          auto issue_pair = [&](int64_t pi, int ps) {
+            issue_pair_at(pi < npairs ? pi : npairs - 1, ps);   // prefetch past the end re-reads the last pair
+          };
+          (void)issue_pair;
           // NPW pairs per iteration (pi, pi + stride, ...): the ring holds PS = PF / 2 pair slots, PS - NPW
           // of them in flight while the NPW oldest are trained on.
           static_assert(PS > NPW, "ring: at least one pair in flight");
@@ -1578,6 +1593,64 @@ __global__ __launch_bounds__(WAVES * 64, OCC) void ae_train_kernel(AEArgs a) {
               ix[0] = ix[1] = a.want_acc ? row_argmax_up_pair_signed(xf[0][0], xf[1][0], xup, g) : -1;
             }
           };
+          (void)load_pair;
+          // (the 3-wave builds' three-slot ring and the raw-row variants spill with it and keep the
+          // rolled loop below)
+          if constexpr (NPW == 1 && XM == 1 && PS == 2) {
+            // One pair per trip, two pair slots: the loop control is wave-uniform and 32-bit (the launcher bounds the
+            // pair count), so it stays on the scalar unit -- the trip count once, the prefetch index
+            // clamped by a scalar min -- and the loop is unrolled by the ring depth, so trip j reads
+            // pair slot j % PS and fills slot (j - 1) % PS as compile-time LDS offsets.  Same pairs in
+            // the same order per wave, same DMA and vmcnt counts as the rolled loop.
+            const unsigned np32 = (unsigned)npairs, st32 = (unsigned)stride, uf32 = (unsigned)ufirst;
+            const unsigned ntrip = __builtin_amdgcn_readfirstlane(uf32 < np32 ? (np32 - 1u - uf32) / st32 + 1u : 0u);
+            unsigned pq = uf32;   // next pair to prefetch
+            auto issue_next = [&](int ps) {
+              issue_pair_at(pq < np32 ? pq : np32 - 1u, ps);   // past the end: re-read the last pair
+              pq += st32;
+            };
+#pragma unroll
+            for (int k = 0; k < PS - 1; ++k) issue_next(k);
+            // the lane's three ring addresses, each ONE register for the whole loop (opaque to the
+            // compiler, so every slot is base + immediate and no per-slot copy of them is kept)
+            lds_cc* rowb = (lds_cc*)(ring + row_off);
+            lds_cc* upb = (lds_cc*)(ring + up_off);
+            lds_cc* axb = (lds_cc*)(ring + (slotb - 16) + c);   // XM 1: the tile's argmax byte of row c
+            asm volatile("" : "+v"(rowb), "+v"(upb));
+            asm volatile("" : "+v"(axb));
+            auto trip = [&](auto slot) {
+              constexpr int rs = decltype(slot)::value, ws = (rs + PS - 1) % PS;
+              issue_next(ws);
+              asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NVP * (PS - 1)) : "memory");
+              typedef __attribute__((address_space(3))) const unsigned char lds_u8;
+              typedef __attribute__((address_space(3))) const float lds_f;
+              f32x4 xf[1][2][2];
+              float xup[1];
+              int ix[1][2];
+              lds_cc* const xr[1] = {rowb + 2 * rs * slotb};
+              lds_cc* const xu[1] = {upb + 2 * rs * slotb};
+#pragma unroll
+              for (int u = 0; u < 2; ++u) {
+                xf[0][u][0] = ring_row4(xr[0] + u * slotb);
+                xf[0][u][1] = f32x4{0.f, 0.f, 0.f, 0.f};
+                ix[0][u] = (int)*(lds_u8*)(axb + (2 * rs + u) * slotb);
+              }
+              xup[0] = *(lds_f*)xu[0];
+              constexpr bool RX = OCC >= 4;
+              train_pair_packed<PACK, DC, false, TS, 1, XP, RX, CMP, true, false>(
+                  a, FP, scr, c, g, xf, xup, ix, acc1, acc2, acc3, acc4, acc2b, acc4b, sq, ab, corr, rows, xr, xu);
+            };
+            // one copy of each slot's trip: the wave leaves the unrolled body after its last trip
+            for (unsigned k = ntrip; k > 0; k -= PS) {
+              trip(RingSlot<0>{});
+              if (k == 1) break;
+              trip(RingSlot<1>{});
+            }
+            // two rows of row-counting lane group 0 per trip: an exact small integer, as the
+            // per-trip adds were
+            rows += (g == 0) ? 2.f * (float)ntrip : 0.f;
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // no DMA may land after the ring is retired
+          } else {
           int64_t pp = ufirst;
 #pragma unroll
           for (int k = 0; k < PS - NPW; ++k) {
@@ -1597,16 +1670,19 @@ __global__ __launch_bounds__(WAVES * 64, OCC) void ae_train_kernel(AEArgs a) {
             f32x4 xf[NPW][2][2];
             float xup[NPW];
             int ix[NPW][2];
-            const char* xr[NPW];
+            lds_cc* xr[NPW];
+            lds_cc* xu[NPW];
 #pragma unroll
             for (int k = 0; k < NPW; ++k) {
               load_pair(rs, xf[k], xup[k], ix[k]);
-              xr[k] = ring + 2 * rs * slotb;
+              xr[k] = (lds_cc*)(ring + 2 * rs * slotb + row_off);
+              xu[k] = (lds_cc*)(ring + 2 * rs * slotb + up_off);
               rs = rs + 1 == PS ? 0 : rs + 1;
             }
             constexpr bool RX = XM == 1 && OCC >= 4;
-            train_pair_packed<PACK, DC, false, TS, NPW, XP, RX, CMP>(a, FP, scr, c, g, xf, xup, ix, acc1, acc2, acc3,
-                                                                     acc4, acc2b, acc4b, sq, ab, corr, rows, xr);
+            train_pair_packed<PACK, DC, false, TS, NPW, XP, RX, CMP, XM == 1>(a, FP, scr, c, g, xf, xup, ix, acc1, acc2,
+                                                                              acc3, acc4, acc2b, acc4b, sq, ab, corr,
+                                                                              rows, xr, xu);
           }
           if (NPW == 2 && pi < npairs) {   // a last lone pair: the oldest of the PS - NPW in flight
             static_assert(NPW == 1 || PS - NPW - 1 >= 0, "ring depth");
@@ -1615,10 +1691,12 @@ __global__ __launch_bounds__(WAVES * 64, OCC) void ae_train_kernel(AEArgs a) {
             float xup[1];
             int ix[1][2];
             load_pair(rs, xf[0], xup[0], ix[0]);
-            train_pair_packed<PACK, DC, false, TS, 1, XP, false, CMP>(a, FP, scr, c, g, xf, xup, ix, acc1, acc2, acc3,
-                                                                      acc4, acc2b, acc4b, sq, ab, corr, rows);
+            train_pair_packed<PACK, DC, false, TS, 1, XP, false, CMP, XM == 1>(a, FP, scr, c, g, xf, xup, ix, acc1, acc2,
+                                                                               acc3, acc4, acc2b, acc4b, sq, ab, corr,
+                                                                               rows);
           }
           asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // no DMA may land after the ring is retired
+          }
         } else {
         int64_t tp = t0;
 #pragma unroll
@@ -2208,6 +2286,10 @@ hipError_t ae_train_launch(const float* x, int64_t n, int64_t ld, const float* s
     // so refuse to silently train on x when none of them applies.
     // xpack_live: the features the packed ring stores (0 = all D).  Only the packed-pair variants
     // read the compact ring of the cardata live set; any other mask, or any other variant, is refused.
+    // That mask means the LANE-ORDERED compact layout (pack_tiles_argmax with lane_order, what
+    // FusedAE builds): no kernel reads the ascending compact layout.
+    // the pair loops count pairs in 32 bits (2^30 pairs = 2^35 rows: past any device's memory)
+    if ((n >> 5) >= (int64_t(1) << 30)) return hipErrorInvalidValue;
     const bool pairs_ok = ((n >> 4) & 1) == 0 && train_ilp() == 3 && dims[1] <= 15 && dims[2] <= 7 && dims[3] <= 7;
     const bool full = xpack_live == 0 || (D <= 31 && xpack_live == (1u << D) - 1u);
     const bool cm = !full && D == 18 && xpack_live == kLiveCardata;

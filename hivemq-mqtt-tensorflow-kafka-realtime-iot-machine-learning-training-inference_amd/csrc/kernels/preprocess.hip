@@ -209,7 +209,9 @@ __device__ __forceinline__ void load_tables(float* s_sc, float* s_sh, int period
 
 // MODE 0: tile-pack (rows + argmax bytes per 16-row tile); MODE 1: argmax bytes only.
 // MODE 2: compact tile-pack.  `live` is a bit mask of the features the tile keeps: per 16-row
-// tile 16 rows x popcount(live) floats, the live features in ascending order, then the same 16
+// tile 16 rows x popcount(live) floats, the live features in ascending order (or, with
+// `lane_order`, the cardata live set in the order the packed-pair train loop's lanes read it:
+// features 16, 1, 17, 3, 6, 7, ..., 15), then the same 16
 // argmax bytes (taken over all D normalised values, original feature numbering).  The columns
 // left out are the ones the normaliser assigns a constant 0 (scale = shift = 0, the reference's
 // normalize_fn), and they enter the argmax as that constant, not as raw * 0 + 0: a NaN or Inf
@@ -219,7 +221,7 @@ __global__ __launch_bounds__(kThreads) void rows_group_kernel(const float* __res
                                                               int Drt, const float* __restrict__ scale,
                                                               const float* __restrict__ shift,
                                                               uint8_t* __restrict__ out, RowSource src,
-                                                              int vec2, uint64_t live) {
+                                                              int vec2, uint64_t live, int lane_order) {
   const int D = DT > 0 ? DT : Drt;
   __shared__ int s_col[64];   // MODE 2: compact column k -> feature
   const int nlive = MODE == 2 ? __popcll(live) : D;
@@ -230,6 +232,10 @@ __global__ __launch_bounds__(kThreads) void rows_group_kernel(const float* __res
         if (k == 0) col = f;
         --k;
       }
+    if (lane_order) {   // D = 18, the cardata live set (checked by the launcher)
+      k = (int)threadIdx.x;
+      col = k == 0 ? 16 : k == 2 ? 17 : k < 4 ? k : k < 14 ? k + 2 : 0;
+    }
     s_col[threadIdx.x] = col;
   }
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -311,7 +317,7 @@ int stream_grid(int64_t groups_of_waves) {
 template <int MODE>
 hipError_t launch_rows_group(const float* x, int64_t n, int64_t ld, int D, const float* scale, const float* shift,
                              uint8_t* out, hipStream_t stream, RowSource src = RowSource{nullptr, 0, 0, 0},
-                             uint64_t live = 0) {
+                             uint64_t live = 0, int lane_order = 0) {
   const bool gather = src.index != nullptr || src.half > 0;
   const bool contig = !gather && ld == D && (reinterpret_cast<uintptr_t>(x) & 15) == 0;
   const int vec2 = (ld & 1) == 0 && (reinterpret_cast<uintptr_t>(x) & 7) == 0;
@@ -337,16 +343,16 @@ hipError_t launch_rows_group(const float* x, int64_t n, int64_t ld, int D, const
   }
   if (D == 18 && contig)
     hipLaunchKernelGGL((rows_group_kernel<18, true, MODE>), grid, block, lds, stream, x, n, ld, D, scale, shift, out,
-                       src, vec2, live);
+                       src, vec2, live, lane_order);
   else if (contig)
     hipLaunchKernelGGL((rows_group_kernel<0, true, MODE>), grid, block, lds, stream, x, n, ld, D, scale, shift, out,
-                       src, vec2, live);
+                       src, vec2, live, lane_order);
   else if (D == 18)
     hipLaunchKernelGGL((rows_group_kernel<18, false, MODE>), grid, block, lds, stream, x, n, ld, D, scale, shift, out,
-                       src, vec2, live);
+                       src, vec2, live, lane_order);
   else
     hipLaunchKernelGGL((rows_group_kernel<0, false, MODE>), grid, block, lds, stream, x, n, ld, D, scale, shift, out,
-                       src, vec2, live);
+                       src, vec2, live, lane_order);
   return hipGetLastError();
 }
 
@@ -509,7 +515,7 @@ hipError_t normalize_filter_launch(const float* x, int64_t n, int64_t ld, int D,
 
 hipError_t pack_tiles_argmax_launch(const float* x, int64_t n, int64_t ld, int D, const float* scale,
                                     const float* shift, uint8_t* out, hipStream_t stream, const int64_t* index,
-                                    uint64_t perm_key, int64_t perm_n, uint64_t live_mask) {
+                                    uint64_t perm_key, int64_t perm_n, uint64_t live_mask, bool lane_order) {
   if (n <= 0) return hipSuccess;
   if ((n & 15) || D < 1 || D > 64) return hipErrorInvalidValue;
   if (reinterpret_cast<uintptr_t>(out) & 15) return hipErrorInvalidValue;
@@ -517,8 +523,11 @@ hipError_t pack_tiles_argmax_launch(const float* x, int64_t n, int64_t ld, int D
   const RowSource src{index, perm_key, perm_n, perm_n > 0 ? perm_half_bits(perm_n) : 0};
   const uint64_t all = D == 64 ? ~0ull : (1ull << D) - 1ull;
   if (live_mask & ~all) return hipErrorInvalidValue;
+  // lane order is defined for the cardata live set of D = 18 only (the layout the train kernel reads)
+  constexpr uint64_t kLaneOrderLive = 0x3FFFFull & ~((1ull << 0) | (1ull << 2) | (1ull << 4) | (1ull << 5));
+  if (lane_order && (D != 18 || live_mask != kLaneOrderLive)) return hipErrorInvalidValue;
   if (live_mask != 0 && live_mask != all)   // compact tiles: the live features only
-    return launch_rows_group<2>(x, n, ld, D, scale, shift, out, stream, src, live_mask);
+    return launch_rows_group<2>(x, n, ld, D, scale, shift, out, stream, src, live_mask, lane_order ? 1 : 0);
   return launch_rows_group<0>(x, n, ld, D, scale, shift, out, stream, src);
 }
 

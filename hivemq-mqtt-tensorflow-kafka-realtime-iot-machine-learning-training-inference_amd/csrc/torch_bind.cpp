@@ -135,10 +135,12 @@ int64_t ae_train_partials(const at::Tensor& x, const c10::optional<at::Tensor>& 
 // argmax bytes per tile.  The features left out are the ones the normaliser zeroes: they are
 // taken as the constant 0 (not raw * 0 + 0), so a NaN / Inf in a raw dead column does not poison
 // the row -- as in the reference, whose normalize_fn assigns a constant.
+// lane_order (D = 18, the cardata live set): the row's 14 floats as features 16, 1, 17, 3, 6..15,
+// the layout the compact train kernels read.
 at::Tensor pack_tiles_argmax(const at::Tensor& x, int64_t D, const c10::optional<at::Tensor>& scale,
                              const c10::optional<at::Tensor>& shift, const c10::optional<at::Tensor>& index,
                              const c10::optional<at::Tensor>& out_opt, uint64_t perm_key, int64_t perm_n,
-                             int64_t n_rows, uint64_t live_mask) {
+                             int64_t n_rows, uint64_t live_mask, bool lane_order) {
   check_dev(x, "x", at::kFloat);
   TORCH_CHECK(x.dim() == 2 && x.stride(1) == 1 && x.size(1) >= D && D >= 1 && D <= 64,
               "x must be [n, >=D] with D <= 64");
@@ -170,6 +172,7 @@ at::Tensor pack_tiles_argmax(const at::Tensor& x, int64_t D, const c10::optional
   TORCH_CHECK(n % 16 == 0, "packed rows must be a multiple of 16");
   const uint64_t all = D == 64 ? ~0ull : (1ull << D) - 1ull;
   TORCH_CHECK((live_mask & ~all) == 0, "live_mask has bits past D");
+  TORCH_CHECK(!lane_order || (D == 18 && live_mask == 0x3FFCAull), "lane_order: D = 18 and the cardata live set only");
   const int64_t cols = live_mask ? __builtin_popcountll(live_mask) : D;
   const int64_t bytes = n / 16 * (64 * cols + 16);
   c10::hip::HIPGuard guard(x.device().index());
@@ -184,7 +187,7 @@ at::Tensor pack_tiles_argmax(const at::Tensor& x, int64_t D, const c10::optional
   }
   SML_CHECK_HIP(sml::pack_tiles_argmax_launch(x.data_ptr<float>(), n, x.stride(0), (int)D, opt_ptr(scale),
                                               opt_ptr(shift), out.data_ptr<uint8_t>(), cur_stream(x), idx, perm_key,
-                                              perm_n, live_mask));
+                                              perm_n, live_mask, lane_order));
   return out;
 }
 
@@ -1467,7 +1470,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("pack_tiles_argmax", &pack_tiles_argmax, "tile-packed training ring (rows + ingest-time argmax per tile)",
         py::arg("x"), py::arg("D"), py::arg("scale") = py::none(), py::arg("shift") = py::none(),
         py::arg("index") = py::none(), py::arg("out") = py::none(), py::arg("perm_key") = 0,
-        py::arg("perm_n") = 0, py::arg("n_rows") = -1, py::arg("live_mask") = 0);
+        py::arg("perm_n") = 0, py::arg("n_rows") = -1, py::arg("live_mask") = 0,
+        py::arg("lane_order") = false);
   m.def("perm_indices", &perm_indices, "the pack's keyed row bijection of [0, n), materialised", py::arg("like"),
         py::arg("n"), py::arg("key"), py::arg("start") = 0, py::arg("count") = -1);
   m.def("row_argmax_u8", &row_argmax_u8, "ingest-time argmax of each normalised row (uint8)", py::arg("x"),

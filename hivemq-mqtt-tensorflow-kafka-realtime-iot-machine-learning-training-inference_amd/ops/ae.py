@@ -219,7 +219,7 @@ class FusedAE:
         if self._xpack_ok(ring.size(0), batch) and ring.size(1) == self.spec.input_dim:
             self.ring_live = self._compact_mask(batch)
             self.ring_xpack = self.C.pack_tiles_argmax(ring, self.spec.input_dim, self.scale, self.shift,
-                                                       live_mask=self.ring_live)
+                                                       live_mask=self.ring_live, lane_order=self.ring_live != 0)
 
     # The features the reference's normalize_fn keeps (cardata NORMALIZE_RANGES is None for
     # coolant_temp, intake_air_flow_speed, battery_voltage and current_draw: indices 0, 2, 4, 5).
@@ -227,7 +227,8 @@ class FusedAE:
 
     def _compact_mask(self, batch: int) -> int:
         """Live-feature mask of the compact packed ring, or 0 for the 18-column layout.  The
-        compact ring (14 floats per row: the columns the normaliser zeroes are left out) is read
+        compact ring (14 floats per row: the columns the normaliser zeroes are left out, the rest in
+        the lane order of the train loop -- ``pack_tiles_argmax(..., lane_order=True)``) is read
         by the packed-pair kernel only: an even tile count per batch, ``SML_AE_ILP`` unset or 3,
         hidden layers <= 7 wide, and a normaliser whose dead set (scale == shift == 0) is exactly
         cardata's.  ``SML_AE_COMPACT=0`` keeps the 18-column layout (A/B; read when the ring is
@@ -275,11 +276,11 @@ class FusedAE:
         if perm_key is not None:
             self.C.pack_tiles_argmax(x, self.spec.input_dim, self.scale, self.shift, None, buf,
                                      perm_key=int(perm_key) & ((1 << 64) - 1), perm_n=int(x.size(0)), n_rows=rows,
-                                     live_mask=live)
+                                     live_mask=live, lane_order=live != 0)
         else:
             idx = index[:rows].contiguous() if index is not None else None
             self.C.pack_tiles_argmax(x if idx is not None else x[:rows], self.spec.input_dim, self.scale, self.shift,
-                                     idx, buf, live_mask=live)
+                                     idx, buf, live_mask=live, lane_order=live != 0)
         # the ring tensor only carries the geometry (rows, stride): with a packed ring the
         # launcher reads the rows from the pack alone and refuses any variant that would not
         self.ring, self.ring_batch = x[:rows], B

@@ -15,6 +15,7 @@ typedef __attribute__((__vector_size__(4 * sizeof(float)))) float f32x4;
 #define FMA(r) asm volatile("v_fma_f32 %0, %1, %2, %0" : "+v"(r) : "v"(x), "v"(y))
 #define EXP(r) asm volatile("v_exp_f32 %0, %0" : "+v"(r))
 #define CVT(r, s) asm volatile("v_cvt_pk_bf16_f32 %0, %0, %1" : "+v"(r) : "v"(s))
+#define PERM(r, s) asm volatile("v_perm_b32 %0, %1, %0, %2" : "+v"(r) : "v"(s), "s"(0x07060302))
 
 template <int MODE>
 __global__ __launch_bounds__(256) void probe(int iters, float x, float y, float* out, long long* cyc) {
@@ -41,6 +42,9 @@ __global__ __launch_bounds__(256) void probe(int iters, float x, float y, float*
     } else if constexpr (MODE == 4) {   // 16 independent cvt_pk_bf16
       CVT(a0, a1); CVT(a1, a2); CVT(a2, a3); CVT(a3, a4); CVT(a4, a5); CVT(a5, a6); CVT(a6, a7); CVT(a7, a0);
       CVT(a0, a1); CVT(a1, a2); CVT(a2, a3); CVT(a3, a4); CVT(a4, a5); CVT(a5, a6); CVT(a6, a7); CVT(a7, a0);
+    } else if constexpr (MODE == 6) {   // 16 independent v_perm_b32 (the high halves of two fp32: a bf16 pair)
+      PERM(a0, a1); PERM(a1, a2); PERM(a2, a3); PERM(a3, a4); PERM(a4, a5); PERM(a5, a6); PERM(a6, a7); PERM(a7, a0);
+      PERM(a0, a1); PERM(a1, a2); PERM(a2, a3); PERM(a3, a4); PERM(a4, a5); PERM(a5, a6); PERM(a6, a7); PERM(a7, a0);
     } else {   // 4 dependent chains of 4 FMAs each, chains interleaved (ILP 4)
       FMA(a0); FMA(a1); FMA(a2); FMA(a3); FMA(a0); FMA(a1); FMA(a2); FMA(a3);
       FMA(a0); FMA(a1); FMA(a2); FMA(a3); FMA(a0); FMA(a1); FMA(a2); FMA(a3);
@@ -101,5 +105,6 @@ int main(int argc, char** argv) {
   run<2>("exp8_fma8", cus, iters);
   run<3>("mfma2_fma14", cus, iters);
   run<4>("cvt_pk16", cus, iters);
+  run<6>("perm_b32_16", cus, iters);
   return 0;
 }
