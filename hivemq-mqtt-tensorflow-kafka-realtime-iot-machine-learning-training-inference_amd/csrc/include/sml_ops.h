@@ -58,6 +58,18 @@ hipError_t lstm_fwd_launch(const float* zx, const float* Uw, const float* h0, co
 hipError_t lstm_bwd_launch(const float* dh, const float* gates, const float* cseq, const float* c0, const float* Uw,
                            float* dz, float* dh0, float* dc0, int64_t B, int T, int U, int act, hipStream_t stream);
 
+// ---- LSTM recurrence, 128 < U <= 512 in steps of 64 (lstm_wide.hip) ----
+// The recurrent weight is streamed from a bf16 fragment-ordered image that each launcher
+// packs into `image` (lstm_wide_image_bytes(U) bytes of device scratch) before its kernel.
+bool lstm_wide_supported(int U);
+int64_t lstm_wide_image_bytes(int U);
+hipError_t lstm_wide_fwd_launch(const float* zx, const float* Uw, void* image, const float* h0, const float* c0,
+                                float* hseq, float* cseq, float* gates, int64_t B, int T, int U, int act,
+                                hipStream_t stream);
+hipError_t lstm_wide_bwd_launch(const float* dh, const float* gates, const float* cseq, const float* c0,
+                                const float* Uw, void* image, float* dz, float* dh0, float* dc0, int64_t B, int T,
+                                int U, int act, hipStream_t stream);
+
 // ---- softmax + sparse categorical cross-entropy (softmax_xent.hip) ----
 hipError_t softmax_xent_launch(const float* logits, const int64_t* labels, int64_t B, int C, float gscale,
                                float* dlogits, float* probs, float* acc, hipStream_t stream);

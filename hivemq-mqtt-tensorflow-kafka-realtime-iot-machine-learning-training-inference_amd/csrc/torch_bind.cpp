@@ -545,8 +545,9 @@ std::vector<at::Tensor> lstm_fwd(const at::Tensor& zx, const at::Tensor& Uw, con
   TORCH_CHECK(Uw.dim() == 2 && Uw.is_contiguous() && Uw.size(1) == 4 * Uw.size(0), "U must be [u, 4u]");
   const int64_t B = zx.size(0), T = zx.size(1), U = Uw.size(0);
   TORCH_CHECK(zx.size(2) == 4 * U, "zx last dim must be 4u");
-  TORCH_CHECK(U == 16 || U == 32 || U == 64 || U == 128,
-              "LSTM units must be 16, 32, 64 or 128 (ops/lstm.py zero-pads other widths up to one of them)");
+  TORCH_CHECK(U == 16 || U == 32 || U == 64 || U == 128 || sml::lstm_wide_supported((int)U),
+              "LSTM units must be 16, 32, 64, 128 or a multiple of 64 up to 512 (ops/lstm.py zero-pads other "
+              "widths up to one of them)");
   TORCH_CHECK(act == 1 || act == 2, "LSTM activation must be relu or tanh");
   TORCH_CHECK(T >= 1 && B >= 1, "empty input");
   if (h0.has_value()) TORCH_CHECK(h0->is_contiguous() && h0->numel() == B * U, "h0 must be [B, u]");
@@ -555,6 +556,14 @@ std::vector<at::Tensor> lstm_fwd(const at::Tensor& zx, const at::Tensor& Uw, con
   auto h = at::empty({B, T, U}, zx.options());
   auto c = at::empty({B, T, U}, zx.options());
   auto gt = at::empty({B, T, 4 * U}, zx.options());
+  if (sml::lstm_wide_supported((int)U)) {   // U streamed from a fragment-ordered bf16 image (lstm_wide.hip)
+    auto img = at::empty({sml::lstm_wide_image_bytes((int)U)}, zx.options().dtype(at::kByte));
+    SML_CHECK_HIP(sml::lstm_wide_fwd_launch(zx.data_ptr<float>(), Uw.data_ptr<float>(), img.data_ptr(), opt_ptr(h0),
+                                            opt_ptr(c0), h.data_ptr<float>(), c.data_ptr<float>(),
+                                            gt.data_ptr<float>(), B, (int)T, (int)U, (int)act,
+                                            cur_stream(zx)));
+    return {h, c, gt};
+  }
   SML_CHECK_HIP(sml::lstm_fwd_launch(zx.data_ptr<float>(), Uw.data_ptr<float>(), opt_ptr(h0), opt_ptr(c0),
                                      h.data_ptr<float>(), c.data_ptr<float>(), gt.data_ptr<float>(), B, (int)T,
                                      (int)U, (int)act, cur_stream(zx)));
@@ -571,8 +580,9 @@ std::vector<at::Tensor> lstm_bwd(const at::Tensor& dh, const at::Tensor& gates, 
   const int64_t B = dh.size(0), T = dh.size(1), U = Uw.size(0);
   TORCH_CHECK(dh.is_contiguous() && gates.is_contiguous() && cseq.is_contiguous(), "inputs must be contiguous");
   TORCH_CHECK(dh.sizes() == cseq.sizes() && gates.size(2) == 4 * U && dh.size(2) == U, "shape mismatch");
-  TORCH_CHECK(U == 16 || U == 32 || U == 64 || U == 128,
-              "LSTM units must be 16, 32, 64 or 128 (ops/lstm.py zero-pads other widths up to one of them)");
+  TORCH_CHECK(U == 16 || U == 32 || U == 64 || U == 128 || sml::lstm_wide_supported((int)U),
+              "LSTM units must be 16, 32, 64, 128 or a multiple of 64 up to 512 (ops/lstm.py zero-pads other "
+              "widths up to one of them)");
   if (c0.has_value()) TORCH_CHECK(c0->is_contiguous() && c0->numel() == B * U, "c0 must be [B, u]");
   c10::hip::HIPGuard guard(dh.device().index());
   auto dz = at::empty({B, T, 4 * U}, dh.options());
@@ -580,6 +590,16 @@ std::vector<at::Tensor> lstm_bwd(const at::Tensor& dh, const at::Tensor& gates, 
   if (want_state_grads) {
     dh0 = at::empty({B, U}, dh.options());
     dc0 = at::empty({B, U}, dh.options());
+  }
+  if (sml::lstm_wide_supported((int)U)) {
+    auto img = at::empty({sml::lstm_wide_image_bytes((int)U)}, dh.options().dtype(at::kByte));
+    SML_CHECK_HIP(sml::lstm_wide_bwd_launch(dh.data_ptr<float>(), gates.data_ptr<float>(), cseq.data_ptr<float>(),
+                                            opt_ptr(c0), Uw.data_ptr<float>(), img.data_ptr(), dz.data_ptr<float>(),
+                                            want_state_grads ? dh0.data_ptr<float>() : nullptr,
+                                            want_state_grads ? dc0.data_ptr<float>() : nullptr, B, (int)T, (int)U,
+                                            (int)act, cur_stream(dh)));
+    if (want_state_grads) return {dz, dh0, dc0};
+    return {dz};
   }
   SML_CHECK_HIP(sml::lstm_bwd_launch(dh.data_ptr<float>(), gates.data_ptr<float>(), cseq.data_ptr<float>(),
                                      opt_ptr(c0), Uw.data_ptr<float>(), dz.data_ptr<float>(),

@@ -8,8 +8,11 @@ hand-written kernel (``lstm_dz_wgrad_kernel``, split over gate groups) contracts
 since 4U x (16 KT + U) weight-gradient accumulators do not fit one wave's registers.
 Fallback for shapes without a fused instance (:class:`LSTMFunction`): K1/K2
 projection kernels (the general MFMA GEMM for wide layers) + the recurrence-only kernels
-described below (U = 128: four waves share each 16-sequence tile).  Widths other than
-16 / 32 / 64 / 128 are zero-padded to the next of them (:func:`pad_lstm_weights`: exact).
+described below (U = 128: four waves share each 16-sequence tile; 128 < U <= 512: the
+recurrent weight no longer fits a CU and is streamed from a bf16 fragment-ordered image,
+``csrc/kernels/lstm_wide.hip``).  Widths other than 16 / 32 / 64 / 128 / 192 / 256 / ... / 512
+are zero-padded to the next of them (:func:`pad_lstm_weights`: exact).  Beyond 512 units the
+layer runs on torch ops, counted as a fallback (``SML_STRICT_KERNELS=1`` refuses).
 
 Fallback forward: Zx = X.W + b over all B*T rows (K1 ``dense_fwd``), then the
 ``lstm_fwd`` kernel runs the recurrence (U.h MFMAs + gates + state update per
@@ -140,12 +143,21 @@ def fused_supported(units: int, in_features: int) -> bool:
     return bool(load_c().lstm_fused_supported(int(units), int(in_features)))
 
 
-KERNEL_UNITS = (16, 32, 64, 128)   # widths the recurrence kernels are built for
+KERNEL_UNITS = (16, 32, 64, 128)   # widths of the register-resident recurrence kernels (and the fused layer)
+WIDE_UNITS = (192, 256, 320, 384, 448, 512)   # widths of the streamed-weight recurrence kernels (lstm_wide.hip)
 
 
 def padded_units(units: int):
-    """Smallest kernel width >= ``units`` (None beyond 128)."""
+    """Smallest register-resident kernel width >= ``units`` (None beyond 128)."""
     for p in KERNEL_UNITS:
+        if units <= p:
+            return p
+    return None
+
+
+def kernel_units(units: int):
+    """Smallest width any recurrence kernel is built for >= ``units`` (None beyond 512)."""
+    for p in KERNEL_UNITS + WIDE_UNITS:
         if units <= p:
             return p
     return None
@@ -175,8 +187,8 @@ def lstm(x: torch.Tensor, W: torch.Tensor, U: torch.Tensor, b: torch.Tensor, act
     ``return_sequences=False`` returns h_T [B, U] (Keras semantics)."""
     if x.is_cuda:
         u = U.shape[0]
-        if u not in KERNEL_UNITS:
-            up = padded_units(u)
+        if u not in KERNEL_UNITS and u not in WIDE_UNITS:
+            up = kernel_units(u)
             if up is None:   # wider than any kernel: torch ops (counted; SML_STRICT_KERNELS=1 refuses)
                 from ._ext import note_fallback
                 note_fallback(f"lstm[{u} units]")
