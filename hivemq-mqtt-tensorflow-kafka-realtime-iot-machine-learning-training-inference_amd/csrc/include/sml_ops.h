@@ -16,6 +16,9 @@ hipError_t ae_train_launch(const float* x, int64_t n, int64_t ld, const float* s
                            const int* dims, const int* acts, float l1, int want_acc, int grid, const uint8_t* xpack,
                            hipStream_t stream, int* grid_used,   // grid_used <= grid: slabs written
                            unsigned xpack_live = 0);  // features the packed ring stores (0: all D)
+// the calling thread's last ae_train_launch: (XP, TS) of the 4-wave compact-ring packed-pair
+// instances, -1 for any other variant, and that instance's static LDS bytes
+void ae_train_last_variant(int out[3]);
 // metrics (optional, 4 floats): += (sum sq err, sum |h1|, correct argmax, rows) -- evaluate()
 hipError_t ae_forward_launch(const float* x, int64_t n, int64_t ld, const float* scale, const float* shift,
                              const float* params, float* recon, float* score, uint8_t* flag, float threshold,

@@ -1061,7 +1061,12 @@ __device__ __forceinline__ bf16x4 tr_read(char* slot, int c, int g) {
 // dW2 / dW4 in one accumulator each (MA); 2: no LDS at all -- each operand is the A operand of one
 // 16x16x16 MFMA against the identity (C = A . I is the operand in the rows-on-K C layout, exact in
 // fp32, repacked to bf16 bit-exactly), plus MA; 3: EW for the 7 forward operands (LDS slots 0..6),
-// the MFMA identity for the 7 backward ones, plus MA.  The LDS-transpose loop spends half its issue
+// the MFMA identity for the 7 backward ones, plus MA; 4 (TS 12): XP 3, and the five backward
+// operands that exist before the end of the chain -- dz4b[0..1], dz4bu (packed before d3), dz3b
+// (before d2), dz2b (before d1) -- are written to slots 7..11 as soon as they are packed and read
+// back transposed with the forward ones, the rest of the backward chain hiding the round trip;
+// only dz1b[0..1], produced last, keep the MFMA identity (5 MFMA and 10 cvt_pk fewer per pair, the
+// same bf16 bits).  The LDS-transpose loop spends half its issue
 // stalls waiting to issue LDS instructions (SQ_WAIT_INST_LDS, profiles/r06/SUMMARY.md §1).
 // RX (tile-packed ring only): the fp32 inputs the loss needs (y - x) are read again from the pair's
 // ring slot at the output layer instead of being held in 9 registers across the whole forward
@@ -1089,7 +1094,8 @@ __device__ __forceinline__ void train_pair_packed(const AEArgs& a, const FragsP&
   const bool pad_lane = (g == 3);
   const bool lo = c < 8;   // lanes holding tile 0's half of a packed operand (as n or m = c)
   auto stand_in = [](int p, int u) { return TP && p == NP - 1 && u == 1; };
-  constexpr bool EW = XP == 1 || XP == 3, MA = XP >= 1, TRM = XP == 2;
+  constexpr bool EW = XP == 1 || XP >= 3, MA = XP >= 1, TRM = XP == 2;
+  constexpr bool EB = XP == 4;   // the early backward writes (slots 7..11)
   // identity B operand (lane (n = c, g) holds k = 4g..4g+3): 1 where k == n
   bf16x4 ident;
 #pragma unroll
@@ -1106,9 +1112,9 @@ __device__ __forceinline__ void train_pair_packed(const AEArgs& a, const FragsP&
     // one B operand; layer 1 is one 16x16x32 per tile: [inputs 0..15 | UP + bias]
     xub[p] = pack4(f32x4{xup[p], g == 0 ? 1.0f : 0.0f, 0.f, 0.f});
     if constexpr (EW) {   // slots 0..6 of the pair: the forward operands of the weight gradients
-      tr_write(xb0[p][0], scr + (p * 10 + 0) * 512, c, g);
-      tr_write(xb0[p][1], scr + (p * 10 + 1) * 512, c, g);
-      tr_write(xub[p], scr + (p * 10 + 2) * 512, c, g);
+      tr_write(xb0[p][0], scr + (p * TS + 0) * 512, c, g);
+      tr_write(xb0[p][1], scr + (p * TS + 1) * 512, c, g);
+      tr_write(xub[p], scr + (p * TS + 2) * 512, c, g);
     }
   }
 #pragma unroll
@@ -1137,7 +1143,7 @@ __device__ __forceinline__ void train_pair_packed(const AEArgs& a, const FragsP&
 #pragma unroll
       for (int i = 0; i < 4; ++i) h1[p][u][i] = tanh_exp2(z1[p][u][i]);
       h1b[p][u] = pack4(h1[p][u]);
-      if constexpr (EW) tr_write(h1b[p][u], scr + (p * 10 + 3 + u) * 512, c, g);
+      if constexpr (EW) tr_write(h1b[p][u], scr + (p * TS + 3 + u) * 512, c, g);
     }
   // Keras L1 activity-regulariser gradient l1 * sign(h1) as one v_med3 (see train_tile), computed
   // off the critical path and fed to the dh1 MFMA as its accumulator input (EW: right before it,
@@ -1160,7 +1166,7 @@ __device__ __forceinline__ void train_pair_packed(const AEArgs& a, const FragsP&
 #pragma unroll
     for (int i = 0; i < 4; ++i) h2[p][i] = relu_fast(z2[p][i]);
     h2b[p] = pack4(h2[p]);
-    if constexpr (EW) tr_write(h2b[p], scr + (p * 10 + 5) * 512, c, g);
+    if constexpr (EW) tr_write(h2b[p], scr + (p * TS + 5) * 512, c, g);
   }
 #pragma unroll
   for (int p = 0; p < NP; ++p) z3[p] = mfma16(F.w3t, h2b[p], zero4);
@@ -1169,7 +1175,7 @@ __device__ __forceinline__ void train_pair_packed(const AEArgs& a, const FragsP&
 #pragma unroll
     for (int i = 0; i < 4; ++i) h3[p][i] = tanh_exp2(z3[p][i]);
     h3b[p] = pack4(h3[p]);
-    if constexpr (EW) tr_write(h3b[p], scr + (p * 10 + 6) * 512, c, g);
+    if constexpr (EW) tr_write(h3b[p], scr + (p * TS + 6) * 512, c, g);
   }
   // output layer: outputs 0..15 per tile, outputs 16 / 17 of BOTH tiles in one register (UP:
   // lane group g = output 16 + (g & 1) of tile g >> 1; w4u's rows m = 4q, so only C entry 0 is used)
@@ -1238,6 +1244,11 @@ __device__ __forceinline__ void train_pair_packed(const AEArgs& a, const FragsP&
 #pragma unroll
     for (int u = 0; u < 2; ++u) dz4b[p][u] = pack4(dz4[p][u]);
     dz4bu[p] = pack4(f32x4{dz4up[p], 0.f, 0.f, 0.f});
+    if constexpr (EB) {
+      tr_write(dz4b[p][0], scr + (p * TS + 7) * 512, c, g);
+      tr_write(dz4b[p][1], scr + (p * TS + 8) * 512, c, g);
+      tr_write(dz4bu[p], scr + (p * TS + 9) * 512, c, g);
+    }
   }
 #pragma unroll
   for (int p = 0; p < NP; ++p) {
@@ -1250,6 +1261,7 @@ __device__ __forceinline__ void train_pair_packed(const AEArgs& a, const FragsP&
 #pragma unroll
     for (int i = 0; i < 4; ++i) dz3[i] = d3[p][i] * fmaf(-h3[p][i], h3[p][i], 1.0f);   // 0 at the bias slots (h = 1)
     dz3b[p] = pack4(dz3);
+    if constexpr (EB) tr_write(dz3b[p], scr + (p * TS + 10) * 512, c, g);
   }
 #pragma unroll
   for (int p = 0; p < NP; ++p) d2[p] = mfma16(F.w3b, dz3b[p], zero4);
@@ -1259,6 +1271,7 @@ __device__ __forceinline__ void train_pair_packed(const AEArgs& a, const FragsP&
 #pragma unroll
     for (int i = 0; i < 4; ++i) dz2[i] = h2[p][i] > 0.f ? d2[p][i] : 0.f;
     dz2b[p] = pack4(dz2);
+    if constexpr (EB) tr_write(dz2b[p], scr + (p * TS + 11) * 512, c, g);
   }
   f32x4 d1[NP][2];
   if constexpr (MA) l1_sign();
@@ -1287,14 +1300,35 @@ __device__ __forceinline__ void train_pair_packed(const AEArgs& a, const FragsP&
   // weight gradients (rows on K through the LDS transpose).  Pair p owns slots [p*TS, p*TS + TS);
   // TS < 10: slots k and k + TS share 512 B of scratch -- a wave's LDS operations execute in order,
   // so a later write cannot overtake an earlier transposed read of the same slot
-  // EW: slots 0..6 hold the forward operands written early, 7..9 take the backward ones in turn.
-  static_assert(TS >= 1 && TS <= 10 && (!EW || TS == 10), "transpose slots");
+  // EW: slots 0..6 hold the forward operands written early, 7..9 take the backward ones in turn
+  // (XP 1); XP 4 (TS 12): 7..11 hold dz4b[0..1], dz4bu, dz3b, dz2b, written early too.  Slot reuse
+  // across trips is safe for the same in-order reason: the next trip's write of a slot follows
+  // this trip's read of it in the wave's LDS stream.
+  static_assert(TS >= 1 && TS <= 12 && (!EW || TS == (EB ? 12 : 10)), "transpose slots");
   (void)mfma_tr;
 #pragma unroll
   for (int p = 0; p < NP; ++p) {
     char* sp = scr + p * TS * 512;
     bf16x4 xr0[2], dz1r[2], h1r[2], dz4r[2], xur, dz4ru, dz2r, h2r, dz3r, h3r;
-    if constexpr (TRM) {
+    if constexpr (EB) {
+      // LDS reads return in order (behind the RX re-read of the ring slot), so the operands of
+      // the gradient MFMAs that can go first are asked for first: dW4, dW3, dW2 need nothing
+      // else; dW1's partners dz1r come off the matrix pipe last, so xr0 / xur are read last.
+      h3r = tr_read(sp + 6 * 512, c, g);
+      dz4r[0] = tr_read(sp + 7 * 512, c, g);
+      dz4r[1] = tr_read(sp + 8 * 512, c, g);
+      dz4ru = tr_read(sp + 9 * 512, c, g);
+      h2r = tr_read(sp + 5 * 512, c, g);
+      dz3r = tr_read(sp + 10 * 512, c, g);
+      h1r[0] = tr_read(sp + 3 * 512, c, g);
+      h1r[1] = tr_read(sp + 4 * 512, c, g);
+      dz2r = tr_read(sp + 11 * 512, c, g);
+      xr0[0] = tr_read(sp + 0 * 512, c, g);
+      xr0[1] = tr_read(sp + 1 * 512, c, g);
+      xur = tr_read(sp + 2 * 512, c, g);
+      dz1r[0] = mfma_tr(dz1b[p][0]);
+      dz1r[1] = mfma_tr(dz1b[p][1]);
+    } else if constexpr (TRM) {
       xr0[0] = mfma_tr(xb0[p][0]);
       xr0[1] = mfma_tr(xb0[p][1]);
       xur = mfma_tr(xub[p]);
@@ -1397,7 +1431,10 @@ constexpr int ring_bytes_pf() { return ILP == 3 ? PF * (CM ? 912 : 1168) : ring_
 // Packed pairs (ILP 3): [TS x 512 B transpose scratch per wave | normaliser | rings], and the
 // per-wave gradient slabs written after the loop ALIAS that whole area (the rings are retired
 // with vmcnt(0) and a workgroup barrier first) -- so the loop's LDS is not charged for the slab:
-// OCC 4 (two pair slots, TS 10) is 39 424 B = four workgroups per CU.
+// OCC 4 (two pair slots, TS 10) is 39 424 B = four workgroups per CU on the 18-column ring and 35 328 B
+// on the compact one.  XP 4 (TS 12, the early backward writes) is built for the compact ring only:
+// 39 424 B there; the 18-column and the raw-row 4-wave instances are at 39 424 B with TS 10 already
+// and would drop to three workgroups per CU, so they keep XP 3.
 template <int PF, int OCC, int ILP, int TS, int NPW = 1, int CM = 0>
 struct AELds {
   static constexpr int SCR = (ILP == 3 ? NPW * TS : 10) * 512;      // per wave (0: MFMA transposes)
@@ -1422,7 +1459,8 @@ __global__ __launch_bounds__(WAVES * 64, OCC) void ae_train_kernel(AEArgs a) {
   using L = AELds<PF, OCC, ILP, (XP == 2 ? 0 : TS), NPW, CM>;
   static_assert(NPW == 1 || ILP == 3, "several pairs per iteration: packed pairs only");
   constexpr int RING = L::RING;
-  static_assert(WAVES * 10 * 512 <= SLAB_BYTES, "transpose scratch must fit in the slab buffer");
+  static_assert(WAVES * (ILP == 3 && NPW == 1 ? TS : 10) * 512 <= SLAB_BYTES,
+                "transpose scratch must fit in the slab buffer");
   static_assert(ILP == 3 || TS == 10, "shared transpose slots: packed pairs only");
   static_assert(PF == 0 || CMP || PF * 64 * 17 <= RING, "ring slots must fit the smallest ring tile");
   // XM: x-argmax mode. 0 in-kernel argmax; 1 tile-packed ring (rows + ingest-time argmax
@@ -2191,18 +2229,22 @@ static bool direct_pairs() {
 }
 // SML_AE_PAIR_OCC=2|3|4: waves per SIMD (2: two packed pairs per loop iteration) of the packed-pair kernel on the tile-packed ring
 // (read at every launch, like SML_AE_ILP)
-// Default 4 with XP 3: 4 waves per SIMD, forward operands through early LDS writes and backward
-// ones through the MFMA identity -- 51.6-53.4 vs 48.6-49.5 G rows/s for the round-5 loop (3, XP 0)
-// on the same boxes (profiles/r06/SUMMARY.md §1).
+// Default 4: 4 waves per SIMD, forward operands through early LDS writes and backward
+// ones through the MFMA identity (XP 3) -- 51.6-53.4 vs 48.6-49.5 G rows/s for the round-5 loop
+// (3, XP 0) on the same boxes (profiles/r06/SUMMARY.md §1).
 static int pair_occ() {
   const char* e = getenv("SML_AE_PAIR_OCC");
   return (e && (e[0] == '2' || e[0] == '3' || e[0] == '4')) ? e[0] - '0' : 4;
 }
-// SML_AE_PAIR_XP=0|1|2|3: the packed-pair weight-gradient operand path (train_pair_packed's XP);
-// at SML_AE_PAIR_OCC=4, 0 means 1 (the 4-wave build needs the early writes' registers)
+// SML_AE_PAIR_XP=0|1|2|3|4: the packed-pair weight-gradient operand path (train_pair_packed's XP);
+// at SML_AE_PAIR_OCC=4, 0 means 1 (the 4-wave build needs the early writes' registers).  4 (the
+// early backward writes, TS 12) is built for the compact ring at 4 waves only and means 3
+// everywhere else.  Default 4: 56.78-57.60 vs 55.62-55.67 G rows/s for XP 3 (the parent build) in
+// alternating runs, bit-identical results; SQ_WAIT_INST_LDS rises from 61 to 232 cycles per trip
+// and the wave still spends 183 cycles fewer in a trip (profiles/r10/early_bwd/SUMMARY.md).
 static int pair_xp() {
   const char* e = getenv("SML_AE_PAIR_XP");
-  return (e && e[0] >= '0' && e[0] <= '3') ? e[0] - '0' : 3;
+  return (e && e[0] >= '0' && e[0] <= '4') ? e[0] - '0' : 4;
 }
 static int train_occupancy() {
   const char* e = getenv("SML_AE_OCC");
@@ -2226,6 +2268,22 @@ static int device_cus() {
 int ae_nslot() { return NSLOT; }
 int ae_nparam() { return NPARAM; }
 int ae_waves_per_block() { return WAVES; }
+
+// What the calling thread's last ae_train_launch ran, for tests that A/B two instances in one
+// process: the XP and TS of the 4-wave compact-ring packed-pair instances (-1 for every other
+// variant) and the launched instance's static LDS size as the runtime reports it.
+struct LastVariant {
+  const void* fn = nullptr;
+  int xp = -1, ts = -1;
+};
+static thread_local LastVariant last_variant;
+void ae_train_last_variant(int out[3]) {
+  out[0] = last_variant.xp;
+  out[1] = last_variant.ts;
+  out[2] = -1;
+  hipFuncAttributes attr{};
+  if (last_variant.fn && hipFuncGetAttributes(&attr, last_variant.fn) == hipSuccess) out[2] = (int)attr.sharedSizeBytes;
+}
 
 int ae_train_grid(int64_t n, int max_blocks) {
   const int64_t ntiles = (n + 15) / 16;
@@ -2273,6 +2331,12 @@ hipError_t ae_train_launch(const float* x, int64_t n, int64_t ld, const float* s
     }();
     set_grid(rounds * occ_pairs * device_cus());
   };
+  // the 4-wave compact-ring pair instances say which of them ran (ae_train_last_variant)
+  last_variant = LastVariant{};
+  auto launch_noted = [&](void (*kern)(AEArgs), int xp_, int ts_) {
+    last_variant = LastVariant{reinterpret_cast<const void*>(kern), xp_, ts_};
+    hipLaunchKernelGGL(kern, gd, bd, 0, stream, a);
+  };
   if (pack == PACK_REF) {
     // tile-packed ring with ingest-time x argmax (pack_tiles_argmax): whole 16-row tiles
     const bool xa_ok = xpack != nullptr && want_acc && (n & 15) == 0 &&
@@ -2308,12 +2372,14 @@ hipError_t ae_train_launch(const float* x, int64_t n, int64_t ld, const float* s
       const int po = pair_occ();
       pair_grid(po);
       const int xp = pair_xp();
-      if (cm) {   // the compact-ring twin of every variant below
+      if (cm) {   // the compact-ring twin of every variant below, and the XP 4 instance
         if (po == 2)
           hipLaunchKernelGGL((ae_train_kernel<PACK_REF, true, 8, 2, 18, 1, 3, 10, 2, 0, 1>), gd, bd, 0, stream, a);
+        else if (po == 4 && xp == 4)   // TS 12: 39 424 B, still four workgroups per CU
+          launch_noted(ae_train_kernel<PACK_REF, true, 4, 4, 18, 1, 3, 12, 1, 4, 1>, 4, 12);
         else if (po == 4 && xp >= 2)
-          hipLaunchKernelGGL((ae_train_kernel<PACK_REF, true, 4, 4, 18, 1, 3, 10, 1, 3, 1>), gd, bd, 0, stream, a);
-        else if (xp == 3)
+          launch_noted(ae_train_kernel<PACK_REF, true, 4, 4, 18, 1, 3, 10, 1, 3, 1>, 3, 10);
+        else if (xp >= 3)
           hipLaunchKernelGGL((ae_train_kernel<PACK_REF, true, 6, 3, 18, 1, 3, 10, 1, 3, 1>), gd, bd, 0, stream, a);
         else if (po == 4)
           hipLaunchKernelGGL((ae_train_kernel<PACK_REF, true, 4, 4, 18, 1, 3, 10, 1, 1, 1>), gd, bd, 0, stream, a);
@@ -2327,7 +2393,7 @@ hipError_t ae_train_launch(const float* x, int64_t n, int64_t ld, const float* s
         hipLaunchKernelGGL((ae_train_kernel<PACK_REF, true, 8, 2, 18, 1, 3, 10, 2>), gd, bd, 0, stream, a);
       else if (po == 4 && xp >= 2)   // (XP 2 at 4 waves spills: the MFMA-transpose temporaries)
         hipLaunchKernelGGL((ae_train_kernel<PACK_REF, true, 4, 4, 18, 1, 3, 10, 1, 3>), gd, bd, 0, stream, a);
-      else if (xp == 3)
+      else if (xp >= 3)
         hipLaunchKernelGGL((ae_train_kernel<PACK_REF, true, 6, 3, 18, 1, 3, 10, 1, 3>), gd, bd, 0, stream, a);
       else if (po == 4)
         hipLaunchKernelGGL((ae_train_kernel<PACK_REF, true, 4, 4, 18, 1, 3, 10, 1, 1>), gd, bd, 0, stream, a);
@@ -2353,7 +2419,7 @@ hipError_t ae_train_launch(const float* x, int64_t n, int64_t ld, const float* s
       pair_grid(docc);
       if (docc == 4)
         hipLaunchKernelGGL((ae_train_kernel<PACK_REF, true, 4, 4, 18, 0, 3, 10, 1, 3>), gd, bd, 0, stream, a);
-      else if (pair_xp() == 3)
+      else if (pair_xp() >= 3)
         hipLaunchKernelGGL((ae_train_kernel<PACK_REF, true, 6, 3, 18, 0, 3, 10, 1, 3>), gd, bd, 0, stream, a);
       else
         hipLaunchKernelGGL((ae_train_kernel<PACK_REF, true, 6, 3, 18, 0, 3>), gd, bd, 0, stream, a);

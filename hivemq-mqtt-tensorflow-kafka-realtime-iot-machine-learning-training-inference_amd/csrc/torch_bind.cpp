@@ -1512,6 +1512,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "workgroups per CU the selected AE train-kernel variant keeps resident (SML_AE_OCC)");
   m.def("ae_train_grid", &sml::ae_train_grid, "grid size the AE train kernel uses", py::arg("n"),
         py::arg("max_blocks"));
+  m.def("ae_train_last_variant", [] {
+          int v[3];
+          sml::ae_train_last_variant(v);
+          return std::make_tuple(v[0], v[1], v[2]);
+        },
+        "(XP, TS, LDS bytes) of this thread's last ae_train launch; XP = TS = -1 unless it was a 4-wave "
+        "compact-ring packed-pair instance");
   m.def("reduce_adam", &reduce_adam, "slab reduction + optional Adam", py::arg("partials"), py::arg("G"),
         py::arg("S"), py::arg("nparam"), py::arg("grad_out"), py::arg("params"), py::arg("m"), py::arg("v"),
         py::arg("iter"), py::arg("lr"), py::arg("beta1"), py::arg("beta2"), py::arg("eps"), py::arg("gscale"),
