@@ -109,8 +109,13 @@ def _predict(ns, servers, cfg, rows, model, result_topic):
     # with R > 1) keeps the batch engine under "auto", so both engines return the same shape
     shape = np.shape(model.predict(np.zeros((1, ns.look_back, model.features), np.float32)))[1:]
     one_step = int(np.prod(shape)) == model.features
-    if engine == "auto":
-        engine = "persistent" if model.device.type == "cuda" and one_step else "batch"
+    if engine in ("auto", "persistent"):
+        from ..ops.serve import LSTMScoringServer
+        servable, why = LSTMScoringServer.supports(model)
+        if engine == "auto":   # a stack the forecaster cannot serve (a layer above 512 units ...): batch
+            engine = "persistent" if model.device.type == "cuda" and one_step and servable else "batch"
+        elif not servable:
+            raise SystemExit(f"--predict-engine persistent: the forecaster cannot serve this model: {why}")
     if engine == "persistent":
         out = _predict_persistent(model, rows, b0, len(xw))
         if one_step:

@@ -126,6 +126,14 @@ def seed_group_offsets(client, topic: str, base: str, group: str, partitions, ma
     return seeded
 
 
+def _require_servable(model) -> None:
+    """Exit with the limit the per-event forecaster cannot serve, instead of a traceback."""
+    from ..ops.serve import LSTMScoringServer
+    ok, why = LSTMScoringServer.supports(model)
+    if not ok:
+        raise SystemExit(f"--model lstm: the persistent forecaster cannot serve this model: {why}")
+
+
 def _serve_low_latency(ns, servers, cfg, model, mine, result_parts, summary, rank: int = 0,
                        hash_ranges=None) -> int:
     """One C++ loop per replica over the resident scorer: the autoencoder's, or -- ``--model
@@ -137,6 +145,8 @@ def _serve_low_latency(ns, servers, cfg, model, mine, result_parts, summary, ran
 
     if model.device.type != "cuda":
         raise SystemExit("--low-latency needs a ROCm device (the persistent scorer)")
+    if ns.model == "lstm":
+        _require_servable(model)
     scorer = (LSTMScoringServer(model, nkeys=ns.max_keys, threshold=ns.threshold) if ns.model == "lstm"
               else ScoringServer(model, threshold=ns.threshold))
     with scorer as srv:
@@ -239,6 +249,7 @@ def main(argv: Sequence[str]) -> int:
         if model.device.type != "cuda":
             raise SystemExit("--model lstm serving needs a ROCm device (the persistent forecaster)")
         from ..ops.serve import LSTMScoringServer
+        _require_servable(model)
         forecaster = LSTMScoringServer(model, nkeys=ns.max_keys, threshold=ns.threshold)
     start = -2 if ns.from_beginning else 0
     # every partition listed; the plan keeps this replica's key shares (records of a shared

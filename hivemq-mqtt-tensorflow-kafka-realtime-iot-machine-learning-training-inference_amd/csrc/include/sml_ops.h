@@ -284,9 +284,40 @@ struct LstmServeArgs {
   int nkeys;
   float threshold;
   uint64_t idle_ticks;
+  // wide stacks only (lstm_serve_wide.hip; built once by LSTMServe): per LSTM layer the bf16
+  // images of W and U, the zero-padded fp32 bias, and the [rows, 4 * up] fp32 scratch of the
+  // input projection; null for stacks that take the LDS-resident kernels
+  const uint16_t* wide_w[LS_MAXLAYERS];
+  const uint16_t* wide_u[LS_MAXLAYERS];
+  const float* wide_b[LS_MAXLAYERS];
+  float* wide_zx;
 };
 size_t lstm_serve_lds_bytes(int nw);
 hipError_t lstm_serve_launch(const LstmServeArgs& args, hipStream_t stream);
+// which kernel lstm_serve_launch runs for these arguments (reads SML_LSTM_SERVE_GENERIC)
+enum : int { LSK_REF1 = 0, LSK_PIPE = 1, LSK_GENERIC = 2, LSK_WIDE = 3 };
+int lstm_serve_select(const LstmServeArgs& args);
+
+// ---- wide stacks (lstm_serve_wide.hip): any layer with more than 32 units or inputs ----
+enum : int { LSW_MAXW = 512, LSW_TILE = 32, LSW_MAXT = 64 };
+// widths are zero-padded to the kernel's tile
+constexpr int lstm_serve_wide_pad(int n) { return (n + LSW_TILE - 1) / LSW_TILE * LSW_TILE; }
+// the stack needs the wide kernel: an LSTM layer with u > 32 or in > 32, a head input > 32, or
+// more than four LSTM layers (no LDS-resident kernel takes those)
+bool lstm_serve_is_wide(const LstmServeArgs& args);
+// empty if the wide kernel can run the stack, else the limit it exceeds
+const char* lstm_serve_wide_check(const LstmServeArgs& args);
+// shape of the kernel's buffers: rows x stride bf16 values of LDS sequence, rows x gmax floats of zx
+struct LstmServeWideDims {
+  int rows, stride, gmax;
+};
+LstmServeWideDims lstm_serve_wide_dims(const LstmServeArgs& args);
+size_t lstm_serve_wide_lds_bytes(const LstmServeArgs& args);
+// image of a [K, 4u] fp32 kernel for the wide kernel: K and u zero-padded to Kp and up, rounded to
+// bf16 (nearest even); 16 bytes hold rows 8i .. 8i + 7 of one padded column q * up + j, and
+// the 16-byte groups of a row group are contiguous over the 4 * up columns
+void lstm_serve_wide_image(const float* w, int K, int u, int Kp, int up, uint16_t* out);
+hipError_t lstm_serve_wide_launch(const LstmServeArgs& args, hipStream_t stream);
 
 // ---- fused MSE + categorical accuracy (loss.hip) ----
 bool mse_acc_supported(int F);

@@ -764,43 +764,59 @@ size_t lstm_serve_lds_bytes(int nw) {
          (size_t)MAXLSTM * MAXT * MAXW * sizeof(float) + MAXLSTM * sizeof(int);   // PIPE sequences + counters
 }
 
-hipError_t lstm_serve_launch(const LstmServeArgs& args, hipStream_t stream) {
-  // shape contract of the kernel (also checked by the host class): every layer fits
+namespace {
+// shape contract of the LDS-resident kernels (also checked by the host class): every layer fits
+bool narrow_shape_ok(const LstmServeArgs& args) {
   if (args.D < 1 || args.D > 31 || args.T < 1 || args.T > MAXT || args.nl < 1 || args.nl > LS_MAXLAYERS ||
       args.nslots < 64 || args.nkeys < 1)
-    return hipErrorInvalidValue;
+    return false;
   int nlstm = 0, dim = args.D, tlen = args.T;
   for (int l = 0; l < args.nl; ++l) {
     const LstmServeLayer& L = args.L[l];
     if (L.kind == LS_LSTM) {
-      if (L.in != dim || L.u < 1 || L.u > 32 || L.in > 32 || ++nlstm > MAXLSTM) return hipErrorInvalidValue;
+      if (L.in != dim || L.u < 1 || L.u > 32 || L.in > 32 || ++nlstm > MAXLSTM) return false;
       dim = L.u;
       tlen = L.ret ? tlen : 1;
     } else if (L.kind == LS_REPEAT) {
-      if (tlen != 1 || L.n < 1 || L.n > MAXT) return hipErrorInvalidValue;
+      if (tlen != 1 || L.n < 1 || L.n > MAXT) return false;
       tlen = L.n;
     } else if (L.kind == LS_DENSE) {
-      if (L.in != dim || L.u < 1 || L.u > MAXW) return hipErrorInvalidValue;
+      if (L.in != dim || L.u < 1 || L.u > MAXW) return false;
       dim = L.u;
     } else {
-      return hipErrorInvalidValue;
+      return false;
     }
   }
-  if (args.L[args.nl - 1].kind != LS_DENSE || dim != args.D) return hipErrorInvalidValue;
+  return args.L[args.nl - 1].kind == LS_DENSE && dim == args.D;
+}
+}  // namespace
+
+int lstm_serve_select(const LstmServeArgs& args) {
+  // a layer wider than 32 (units, inputs or the head's input): the streamed-weight kernel
+  if (args.nl < 1 || args.nl > LS_MAXLAYERS) return LSK_GENERIC;   // refused by the launch
+  if (lstm_serve_is_wide(args)) return LSK_WIDE;
   // the reference stack at look_back 1 takes the one-wave register-resident path, unless
   // SML_LSTM_SERVE_GENERIC=1 asks for the general kernel (A/B and cross-checks)
   const char* gen = getenv("SML_LSTM_SERVE_GENERIC");
-  if (lstm_serve_is_ref1(args) && !(gen && gen[0] == '1')) {
+  const bool generic = gen && gen[0] == '1';
+  if (lstm_serve_is_ref1(args) && !generic) return LSK_REF1;
+  // stacks of LSTM layers under one Dense head: the pipelined variant (one wave per layer);
+  // SML_LSTM_SERVE_GENERIC=1 keeps the barrier-per-step kernel (A/B, cross-checks)
+  return pipe_layers(args) > 0 && !generic ? LSK_PIPE : LSK_GENERIC;
+}
+
+hipError_t lstm_serve_launch(const LstmServeArgs& args, hipStream_t stream) {
+  const int which = lstm_serve_select(args);
+  if (which == LSK_WIDE) return lstm_serve_wide_launch(args, stream);
+  if (!narrow_shape_ok(args)) return hipErrorInvalidValue;
+  if (which == LSK_REF1) {
     auto k = args.L[0].act == ACT_RELU ? lstm_serve_ref1_kernel<1> : lstm_serve_ref1_kernel<0>;
     hipLaunchKernelGGL(k, dim3(1), dim3(64), 0, stream, args);
     return hipGetLastError();
   }
   const size_t lds = lstm_serve_lds_bytes(args.nw);
   if (lds + 9 * 1024 > 160 * 1024) return hipErrorInvalidValue;   // + the PIPE kernel's static LDS (8.2 KB)
-  // stacks of LSTM layers under one Dense head: the pipelined variant (one wave per layer);
-  // SML_LSTM_SERVE_GENERIC=1 keeps the barrier-per-step kernel (A/B, cross-checks)
-  const bool pipe = pipe_layers(args) > 0 && !(gen && gen[0] == '1');
-  auto kern = pipe ? lstm_serve_kernel<true> : lstm_serve_kernel<false>;
+  auto kern = which == LSK_PIPE ? lstm_serve_kernel<true> : lstm_serve_kernel<false>;
   if (lds > 65536) {
     const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);

@@ -116,37 +116,98 @@ LSTMServe::LSTMServe(int device, int nslots, const std::vector<float>& weights,
         (L.kind == LS_LSTM && (L.uoff < 0 || (int64_t)L.uoff + (int64_t)L.u * G > (int64_t)weights.size())))
       throw std::invalid_argument("LSTMServe: a layer's weights lie outside the weight vector");
   }
-  if (lstm_serve_lds_bytes((int)weights.size()) > 160 * 1024)
-    throw std::invalid_argument("LSTMServe: the weights do not fit the scorer's LDS");
-  ck(hipMalloc((void**)&wts_d_, weights.size() * sizeof(float)), "hipMalloc weights");
-  ck(hipMemcpy(wts_d_, weights.data(), weights.size() * sizeof(float), hipMemcpyHostToDevice), "copy weights");
-  if (!scale.empty()) {
-    if ((int)scale.size() != D || (int)shift.size() != D) throw std::invalid_argument("LSTMServe: scale/shift size");
-    ck(hipMalloc((void**)&scale_d_, D * sizeof(float)), "hipMalloc scale");
-    ck(hipMalloc((void**)&shift_d_, D * sizeof(float)), "hipMalloc shift");
-    ck(hipMemcpy(scale_d_, scale.data(), D * sizeof(float), hipMemcpyHostToDevice), "copy scale");
-    ck(hipMemcpy(shift_d_, shift.data(), D * sizeof(float), hipMemcpyHostToDevice), "copy shift");
-  }
+  if (!scale.empty() && ((int)scale.size() != D || (int)shift.size() != D))
+    throw std::invalid_argument("LSTMServe: scale/shift size");
   LstmServeArgs& a = args_;
-  a.ctl = ctl_d_;
-  a.req = req_d_;
-  a.res = res_d_;
   a.nslots = nslots_;
-  a.wts = wts_d_;
   a.nw = (int)weights.size();
   a.nl = (int)layers.size();
   for (size_t i = 0; i < layers.size(); ++i) a.L[i] = layers[i];
-  a.scale = scale_d_;
-  a.shift = shift_d_;
   a.D = D;
   a.T = T;
   a.nkeys = nkeys;
   a.threshold = threshold;
   a.idle_ticks = (uint64_t)(idle_seconds * 100e6);   // s_memrealtime runs at 100 MHz
+  // every limit of the kernel that will run, before anything is allocated on the device
+  kernel_ = lstm_serve_select(a);
+  if (kernel_ == LSK_WIDE) {
+    const char* why = lstm_serve_wide_check(a);
+    if (why[0]) throw std::invalid_argument(std::string("LSTMServe: ") + why);
+    if (lstm_serve_wide_lds_bytes(a) + 16 * 1024 > 160 * 1024)
+      throw std::invalid_argument("LSTMServe: the window's sequences do not fit the forecaster's LDS");
+  } else if (lstm_serve_lds_bytes((int)weights.size()) > 160 * 1024) {
+    throw std::invalid_argument("LSTMServe: the weights do not fit the scorer's LDS");
+  }
+  ck(hipMalloc((void**)&wts_d_, weights.size() * sizeof(float)), "hipMalloc weights");
+  ck(hipMemcpy(wts_d_, weights.data(), weights.size() * sizeof(float), hipMemcpyHostToDevice), "copy weights");
+  if (!scale.empty()) {
+    ck(hipMalloc((void**)&scale_d_, D * sizeof(float)), "hipMalloc scale");
+    ck(hipMalloc((void**)&shift_d_, D * sizeof(float)), "hipMalloc shift");
+    ck(hipMemcpy(scale_d_, scale.data(), D * sizeof(float), hipMemcpyHostToDevice), "copy scale");
+    ck(hipMemcpy(shift_d_, shift.data(), D * sizeof(float), hipMemcpyHostToDevice), "copy shift");
+  }
+  a.ctl = ctl_d_;
+  a.req = req_d_;
+  a.res = res_d_;
+  a.wts = wts_d_;
+  a.scale = scale_d_;
+  a.shift = shift_d_;
+  if (kernel_ == LSK_WIDE) build_wide(weights);
   ck(hipMalloc((void**)&a.hist, (size_t)nkeys * T * D * sizeof(float)), "hipMalloc windows");
   ck(hipMalloc((void**)&a.hcount, (size_t)nkeys * sizeof(int)), "hipMalloc counts");
   ck(hipMalloc((void**)&a.lastpred, (size_t)nkeys * D * sizeof(float)), "hipMalloc forecasts");
   reset_keys();   // zeroes the key state and launches the resident kernel
+}
+
+void LSTMServe::build_wide(const std::vector<float>& weights) {
+  // one host image, one allocation, one copy on the server's stream: per LSTM layer the bf16
+  // image of W [Kp, 4 up], of U [up, 4 up], then the fp32 bias [4 up] (all 16-byte aligned:
+  // 4 up is a multiple of 128)
+  LstmServeArgs& a = args_;
+  size_t off[LS_MAXLAYERS][3], total = 0;
+  int li = 0;
+  for (int l = 0; l < a.nl; ++l) {
+    const LstmServeLayer& L = a.L[l];
+    if (L.kind != LS_LSTM) continue;
+    const size_t up = lstm_serve_wide_pad(L.u), kp = lstm_serve_wide_pad(L.in), G = 4 * up;
+    off[li][0] = total;
+    total += kp * G * sizeof(uint16_t);
+    off[li][1] = total;
+    total += up * G * sizeof(uint16_t);
+    off[li][2] = total;
+    total += G * sizeof(float);
+    ++li;
+  }
+  std::vector<unsigned char> img(total, 0);
+  li = 0;
+  for (int l = 0; l < a.nl; ++l) {
+    const LstmServeLayer& L = a.L[l];
+    if (L.kind != LS_LSTM) continue;
+    const int up = lstm_serve_wide_pad(L.u), kp = lstm_serve_wide_pad(L.in);
+    lstm_serve_wide_image(weights.data() + L.woff, L.in, L.u, kp, up,
+                          reinterpret_cast<uint16_t*>(img.data() + off[li][0]));
+    lstm_serve_wide_image(weights.data() + L.uoff, L.u, L.u, up, up,
+                          reinterpret_cast<uint16_t*>(img.data() + off[li][1]));
+    float* b = reinterpret_cast<float*>(img.data() + off[li][2]);
+    for (int q = 0; q < 4; ++q)
+      for (int j = 0; j < L.u; ++j) b[q * up + j] = weights[(size_t)L.boff + q * L.u + j];
+    ++li;
+  }
+  ck(hipMalloc(&wide_d_, total), "hipMalloc weight images");
+  ck(hipMemcpyAsync(wide_d_, img.data(), total, hipMemcpyHostToDevice, stream_), "copy weight images");
+  ck(hipStreamSynchronize(stream_), "sync");
+  for (int i = 0; i < li; ++i) {
+    a.wide_w[i] = reinterpret_cast<const uint16_t*>(static_cast<unsigned char*>(wide_d_) + off[i][0]);
+    a.wide_u[i] = reinterpret_cast<const uint16_t*>(static_cast<unsigned char*>(wide_d_) + off[i][1]);
+    a.wide_b[i] = reinterpret_cast<const float*>(static_cast<unsigned char*>(wide_d_) + off[i][2]);
+  }
+  const LstmServeWideDims d = lstm_serve_wide_dims(a);
+  ck(hipMalloc((void**)&a.wide_zx, (size_t)d.rows * d.gmax * sizeof(float)), "hipMalloc projection scratch");
+}
+
+const char* LSTMServe::kernel() const {
+  static const char* const names[] = {"ref1", "pipe", "generic", "wide"};
+  return names[kernel_];
 }
 
 void LSTMServe::reset_keys() {
@@ -164,6 +225,8 @@ LSTMServe::~LSTMServe() {
     stop();
   } catch (...) {
   }
+  if (wide_d_) (void)hipFree(wide_d_);
+  if (args_.wide_zx) (void)hipFree(args_.wide_zx);
   if (args_.hist) (void)hipFree(args_.hist);
   if (args_.hcount) (void)hipFree(args_.hcount);
   if (args_.lastpred) (void)hipFree(args_.lastpred);

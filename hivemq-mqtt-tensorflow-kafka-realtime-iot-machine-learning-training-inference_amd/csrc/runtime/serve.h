@@ -107,12 +107,19 @@ class LSTMServe : public ServeRing {
   // forget every key's window and forecast: stops the resident kernel, zeroes the key state
   // on the device, relaunches (returns without waiting for the kernel's idle timeout)
   void reset_keys();
+  // the kernel lstm_serve_launch chose for this stack: "ref1" | "pipe" | "generic" | "wide"
+  const char* kernel() const;
 
  protected:
   hipError_t launch_kernel() override;
 
  private:
+  // wide stacks: bf16 images of every LSTM layer's W and U, padded biases (one allocation)
+  // and the input projection's scratch, built once before the resident kernel starts
+  void build_wide(const std::vector<float>& weights);
   LstmServeArgs args_{};
+  int kernel_ = LSK_GENERIC;
+  void* wide_d_ = nullptr;
   float* wts_d_ = nullptr;
   float* scale_d_ = nullptr;
   float* shift_d_ = nullptr;

@@ -1671,6 +1671,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         p.s->stop();   // the kernel must not run while its state is cleared
         static_cast<sml::LSTMServe*>(p.s.get())->reset_keys();
       })
+      .def_property_readonly("kernel",
+                             [](LSTMServePy& p) {
+                               return std::string(static_cast<sml::LSTMServe*>(p.s.get())->kernel());
+                             },
+                             "the kernel lstm_serve_launch chose: ref1 | pipe | generic | wide")
       .def_property_readonly("nkeys", [](LSTMServePy& p) { return p.nk; });
   m.def("lstm_head", &lstm_head, "fused LSTM Dense head: forward, MSE + accuracy, dW / db, dh (one pass + fold)",
         py::arg("h"), py::arg("W"), py::arg("b"), py::arg("y"), py::arg("gscale"), py::arg("grad"), py::arg("map"),

@@ -1,4 +1,5 @@
-"""Persistent per-event scoring on the GPU (``csrc/kernels/ae_serve.hip``, ``lstm_serve.hip``).
+"""Persistent per-event scoring on the GPU (``csrc/kernels/ae_serve.hip``, ``lstm_serve.hip``,
+``lstm_serve_wide.hip``).
 
 ``ScoringServer(model)`` keeps one wave resident on the device that polls a
 host-mapped request ring; ``score(rows)`` publishes rows and spins on the
@@ -103,13 +104,64 @@ def lstm_layer_table(model) -> Tuple[np.ndarray, list]:
 
 
 class LSTMScoringServer:
-    """Persistent per-event LSTM forecaster; ``nkeys`` car keys (ids in [0, nkeys))."""
+    """Persistent per-event LSTM forecaster; ``nkeys`` car keys (ids in [0, nkeys)).
+
+    Stacks whose layers are at most 32 wide run from LDS and registers (``kernel`` is
+    ``"ref1"``, ``"pipe"`` or ``"generic"``, fp32 throughout); anything wider, up to
+    ``MAX_WIDTH`` units or inputs per layer, runs on the streamed-weight kernel (``"wide"``:
+    bf16 weight images, bf16-rounded x and h, fp32 everywhere else; widths zero-padded to
+    ``WIDE_TILE``)."""
+
+    MAX_WIDTH = 512      # LSTM units, layer inputs, head inputs
+    MAX_FEATURES = 31    # request word 31 carries the key
+    MAX_LOOK_BACK = 64
+    MAX_LAYERS = 8
+    WIDE_TILE = 32       # the wide kernel pads every width to a multiple of this
+
+    @staticmethod
+    def supports(model) -> Tuple[bool, str]:
+        """(True, "") if the forecaster can serve ``model``, else (False, the limit it
+        exceeds).  Mirrors the checks of ``LSTMServe``'s constructor; needs no device."""
+        S = LSTMScoringServer
+        if not 1 <= int(model.features) <= S.MAX_FEATURES:
+            return False, f"rows must have 1..{S.MAX_FEATURES} features (request word 31 carries the key)"
+        if not 1 <= int(model.look_back) <= S.MAX_LOOK_BACK:
+            return False, f"look_back must be 1..{S.MAX_LOOK_BACK}"
+        layers = model.layers
+        if not 1 <= len(layers) <= S.MAX_LAYERS:
+            return False, f"1..{S.MAX_LAYERS} layers"
+        lstms = [L for L in layers if L["kind"] == "lstm"]
+        wide = (len(lstms) > 4 or any(L["units"] > 32 or L["in_dim"] > 32 for L in lstms)
+                or any(L["kind"] == "dense" and L["in_dim"] > 32 for L in layers))
+        for L in lstms:
+            if not 1 <= L["units"] <= S.MAX_WIDTH:
+                return False, f"LSTM layers must have 1..{S.MAX_WIDTH} units ({L['name']} has {L['units']})"
+            if L["in_dim"] > S.MAX_WIDTH:
+                return False, f"layer inputs must be 1..{S.MAX_WIDTH} wide ({L['name']} reads {L['in_dim']})"
+        for i, L in enumerate(layers):
+            if L["kind"] == "repeat" and not 1 <= L["n"] <= S.MAX_LOOK_BACK:
+                return False, f"RepeatVector must repeat 1..{S.MAX_LOOK_BACK} times"
+            if L["kind"] == "dense":
+                if L["in_dim"] > S.MAX_WIDTH:
+                    return False, f"the head's input must be 1..{S.MAX_WIDTH} wide"
+                if wide and i != len(layers) - 1:
+                    return False, "a stack with layers wider than 32 takes a Dense layer only as its head"
+                if not wide and L["units"] > 32:
+                    return False, "Dense layers must have 1..32 units"
+        if not lstms:
+            return False, "the stack needs an LSTM layer"
+        if layers[-1]["kind"] != "dense" or layers[-1]["units"] != int(model.features):
+            return False, "the stack must end in a Dense head with one output per feature"
+        return True, ""
 
     def __init__(self, model, nkeys: int = 100_000, threshold: float = 5.0, slots: int = 4096,
                  idle_seconds: float = 2.0, normalizer: Optional[str] = "cardata", device: Optional[torch.device] = None):
         dev = torch.device(device) if device is not None else model.device
         if dev.type != "cuda":
             raise RuntimeError("LSTMScoringServer needs a ROCm device (use LSTMPredictor.predict on CPU)")
+        ok, why = self.supports(model)
+        if not ok:
+            raise ValueError(f"LSTMScoringServer cannot serve this model: {why}")
         flat, table = lstm_layer_table(model)
         sc = sh = None
         if normalizer == "cardata":
@@ -146,6 +198,11 @@ class LSTMScoringServer:
     def reset(self) -> None:
         """Forget every key's window and forecast."""
         self._s.reset_keys()
+
+    @property
+    def kernel(self) -> str:
+        """The resident kernel chosen for this stack: "ref1" | "pipe" | "generic" | "wide"."""
+        return str(self._s.kernel)
 
     @property
     def launches(self) -> int:
