@@ -40,6 +40,9 @@ def _flags(p):
     p.add_argument("--predict-engine", choices=["auto", "persistent", "batch"], default="auto",
                    help="persistent: events one at a time through the resident GPU forecaster "
                         "(lstm_serve.hip); batch: model.predict over the windows; auto: persistent on ROCm")
+    p.add_argument("--lanes", type=int, default=1,
+                   help="persistent engine: resident workgroups of the forecaster (stacks wider than 32 "
+                        "units only; the partition's events are one key, so they all run on lane 0)")
 
 
 def _rows(ns, servers, cfg) -> np.ndarray:
@@ -82,7 +85,7 @@ def _train(ns, rows, model):
     print(f"Training complete ({time.perf_counter() - t0:.2f}s)", flush=True)
 
 
-def _predict_persistent(model, rows: np.ndarray, first: int, count: int) -> np.ndarray:
+def _predict_persistent(model, rows: np.ndarray, first: int, count: int, lanes: int = 1) -> np.ndarray:
     """Forecasts of windows [first, first + count) by streaming the events one at a time
     through the resident forecaster: the window ending at event i is window i - T + 1, so
     events 0 .. first + count + T - 2 are fed (one key: the reference windows the partition's
@@ -92,7 +95,7 @@ def _predict_persistent(model, rows: np.ndarray, first: int, count: int) -> np.n
     end = min(len(rows), first + count + T - 1)
     if end < first + T:
         return np.zeros((0, model.features), np.float32)
-    with LSTMScoringServer(model, nkeys=1, normalizer=None) as srv:   # rows are normalised already
+    with LSTMScoringServer(model, nkeys=1, normalizer=None, lanes=lanes) as srv:   # rows are normalised already
         pred, _, _ = srv.forecast(rows[:end], np.zeros(end, np.int64))
     return pred[first + T - 1:end]
 
@@ -104,6 +107,10 @@ def _predict(ns, servers, cfg, rows, model, result_topic):
     xw = xw[b0:b0 + ns.predict_take * ns.batch_size]
     cbs = [KafkaPredictionSink(ns.batch_size, result_topic, servers, cfg)] if result_topic else []
     engine = ns.predict_engine
+    # --lanes is passed on only when it is not the default: callers that build `ns` by hand and
+    # stand-ins for supports() / _predict_persistent() with the one-lane signatures (the limit
+    # tests patch both in) keep working unchanged
+    lanes = {"lanes": int(ns.lanes)} if int(getattr(ns, "lanes", 1)) != 1 else {}
     # the forecaster emits each window's LAST step only: it serves stacks whose output is one
     # step per window (the reference at look_back 1); a sequence-output stack (RepeatVector(R)
     # with R > 1) keeps the batch engine under "auto", so both engines return the same shape
@@ -111,13 +118,13 @@ def _predict(ns, servers, cfg, rows, model, result_topic):
     one_step = int(np.prod(shape)) == model.features
     if engine in ("auto", "persistent"):
         from ..ops.serve import LSTMScoringServer
-        servable, why = LSTMScoringServer.supports(model)
+        servable, why = LSTMScoringServer.supports(model, **lanes)
         if engine == "auto":   # a stack the forecaster cannot serve (a layer above 512 units ...): batch
             engine = "persistent" if model.device.type == "cuda" and one_step and servable else "batch"
         elif not servable:
             raise SystemExit(f"--predict-engine persistent: the forecaster cannot serve this model: {why}")
     if engine == "persistent":
-        out = _predict_persistent(model, rows, b0, len(xw))
+        out = _predict_persistent(model, rows, b0, len(xw), **lanes)
         if one_step:
             out = out.reshape((len(out),) + tuple(shape))
         for cb in cbs:   # the reference OutputCallback, per batch_size forecasts

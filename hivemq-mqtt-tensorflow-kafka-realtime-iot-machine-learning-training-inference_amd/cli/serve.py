@@ -98,6 +98,9 @@ def _flags(p) -> None:
                    help="lstm: per-car forecaster (look_back events per car on the device, each event "
                         "scored against the car's previous forecast; lstm_serve.hip)")
     p.add_argument("--max-keys", type=int, default=200_000, help="--model lstm: car keys held on the device")
+    p.add_argument("--lanes", type=int, default=1,
+                   help="--model lstm: resident workgroups of the forecaster; car key k is served by lane "
+                        "k %% lanes (stacks wider than 32 units only: lstm_serve_wide.hip)")
     p.add_argument("--source-format", choices=["avro", "json"], default="avro",
                    help="--low-latency: json follows the MQTT bridge's JSON events (sensor-data, KSQL "
                         "SENSOR_DATA_S) directly instead of the Avro stream")
@@ -126,10 +129,10 @@ def seed_group_offsets(client, topic: str, base: str, group: str, partitions, ma
     return seeded
 
 
-def _require_servable(model) -> None:
+def _require_servable(model, lanes: int = 1) -> None:
     """Exit with the limit the per-event forecaster cannot serve, instead of a traceback."""
     from ..ops.serve import LSTMScoringServer
-    ok, why = LSTMScoringServer.supports(model)
+    ok, why = LSTMScoringServer.supports(model, lanes=lanes)
     if not ok:
         raise SystemExit(f"--model lstm: the persistent forecaster cannot serve this model: {why}")
 
@@ -146,9 +149,9 @@ def _serve_low_latency(ns, servers, cfg, model, mine, result_parts, summary, ran
     if model.device.type != "cuda":
         raise SystemExit("--low-latency needs a ROCm device (the persistent scorer)")
     if ns.model == "lstm":
-        _require_servable(model)
-    scorer = (LSTMScoringServer(model, nkeys=ns.max_keys, threshold=ns.threshold) if ns.model == "lstm"
-              else ScoringServer(model, threshold=ns.threshold))
+        _require_servable(model, ns.lanes)
+    scorer = (LSTMScoringServer(model, nkeys=ns.max_keys, threshold=ns.threshold, lanes=ns.lanes)
+              if ns.model == "lstm" else ScoringServer(model, threshold=ns.threshold))
     with scorer as srv:
         starts = None
         if ns.from_beginning:
@@ -249,8 +252,8 @@ def main(argv: Sequence[str]) -> int:
         if model.device.type != "cuda":
             raise SystemExit("--model lstm serving needs a ROCm device (the persistent forecaster)")
         from ..ops.serve import LSTMScoringServer
-        _require_servable(model)
-        forecaster = LSTMScoringServer(model, nkeys=ns.max_keys, threshold=ns.threshold)
+        _require_servable(model, ns.lanes)
+        forecaster = LSTMScoringServer(model, nkeys=ns.max_keys, threshold=ns.threshold, lanes=ns.lanes)
     start = -2 if ns.from_beginning else 0
     # every partition listed; the plan keeps this replica's key shares (records of a shared
     # partition whose car another replica owns are dropped after decode)

@@ -229,8 +229,13 @@ struct alignas(128) ServeCtl {
   uint64_t pad1[15];
   uint32_t stop;            // host: ask the kernel to exit
   uint32_t alive;           // device: 1 while the kernel runs
-  uint32_t pad2[30];
+  // multi-lane forecaster (lstm_serve_wide.hip), lane 0's block only:
+  uint32_t leave;           // device: one-way latch, every lane leaves once it is set; the host
+  uint32_t pad2;            //   clears it before each launch
+  uint64_t active;          // device: s_memrealtime of the latest event pick-up on any lane
+  uint32_t pad3[26];
 };
+static_assert(sizeof(ServeCtl) == 384, "ServeCtl: three 128-byte lines");
 // Request and result slots use low-latency ("LL") framing: every 8-byte word carries
 // 4 bytes of payload and a 4-byte tag = (uint32)(event + 1).  One 8-byte-atomic PCIe
 // read then tells whether the word already belongs to the event being waited for, so
@@ -267,10 +272,12 @@ struct LstmServeLayer {
   int woff, uoff, boff;   // float offsets of kernel / recurrent kernel / bias in the weights
 };
 struct LstmServeArgs {
+  // lanes > 1 (wide stacks only): lane i's control block is ctl[i], its rings are req / res
+  // + i * nslots; stop, leave and active are lane 0's
   ServeCtl* ctl;
   const ServeReq* req;
   ServeResult* res;
-  int nslots;
+  int nslots;          // per lane
   const float* wts;
   int nw;
   int nl;
@@ -281,12 +288,17 @@ struct LstmServeArgs {
   float* hist;         // [nkeys][T][D] per-key window ring (device)
   int* hcount;         // [nkeys] events seen per key
   float* lastpred;     // [nkeys][D] the key's latest forecast
+  // resident workgroups, one per lane (key k is served by lane k % lanes).  It sits here, not
+  // next to nslots: there the wide kernel's argument loads merge into 8-dword tuples that the
+  // register allocator splits, leaving a 32-byte private segment (tests/test_kernel_scratch.py)
+  int lanes;
   int nkeys;
   float threshold;
   uint64_t idle_ticks;
   // wide stacks only (lstm_serve_wide.hip; built once by LSTMServe): per LSTM layer the bf16
-  // images of W and U, the zero-padded fp32 bias, and the [rows, 4 * up] fp32 scratch of the
-  // input projection; null for stacks that take the LDS-resident kernels
+  // images of W and U, the zero-padded fp32 bias, and per lane a [rows, gmax] fp32 scratch of
+  // the input projection (lane i's at wide_zx + i * rows * gmax); null for stacks that take the
+  // LDS-resident kernels
   const uint16_t* wide_w[LS_MAXLAYERS];
   const uint16_t* wide_u[LS_MAXLAYERS];
   const float* wide_b[LS_MAXLAYERS];
@@ -299,7 +311,7 @@ enum : int { LSK_REF1 = 0, LSK_PIPE = 1, LSK_GENERIC = 2, LSK_WIDE = 3 };
 int lstm_serve_select(const LstmServeArgs& args);
 
 // ---- wide stacks (lstm_serve_wide.hip): any layer with more than 32 units or inputs ----
-enum : int { LSW_MAXW = 512, LSW_TILE = 32, LSW_MAXT = 64 };
+enum : int { LSW_MAXW = 512, LSW_TILE = 32, LSW_MAXT = 64, LSW_MAXLANES = 32 };
 // widths are zero-padded to the kernel's tile
 constexpr int lstm_serve_wide_pad(int n) { return (n + LSW_TILE - 1) / LSW_TILE * LSW_TILE; }
 // the stack needs the wide kernel: an LSTM layer with u > 32 or in > 32, a head input > 32, or

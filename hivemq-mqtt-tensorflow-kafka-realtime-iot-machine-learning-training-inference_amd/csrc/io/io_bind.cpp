@@ -14,6 +14,7 @@
 #include "h5.h"
 #include "kafka.h"
 #include "mqtt.h"
+#include "sml_serve_shard.h"
 
 namespace py = pybind11;
 using namespace sml;
@@ -604,6 +605,26 @@ PYBIND11_MODULE(_io, m) {
     fmt::py_float_repr(v, out);
     return out;
   });
+  m.def(
+      "serve_lane_partition",
+      [](py::array_t<int64_t, py::array::c_style | py::array::forcecast> keys, int lanes) {
+        if (keys.ndim() != 1) throw std::invalid_argument("keys must be [k] integers");
+        if (lanes < 1) throw std::invalid_argument("lanes must be >= 1");
+        const ssize_t k = keys.shape(0);
+        std::vector<uint32_t> kv((size_t)k);
+        for (ssize_t i = 0; i < k; ++i) {
+          if (keys.data()[i] < 0 || keys.data()[i] > 0xffffffffLL) throw std::out_of_range("key outside uint32");
+          kv[(size_t)i] = (uint32_t)keys.data()[i];
+        }
+        const ServeLanePartition p = serve_lane_partition(kv.data(), (int)k, lanes);
+        py::array_t<int64_t> order(k), start((ssize_t)lanes + 1);
+        std::copy(p.order.begin(), p.order.end(), order.mutable_data());
+        std::copy(p.start.begin(), p.start.end(), start.mutable_data());
+        return py::make_tuple(order, start);
+      },
+      "the multi-lane forecaster's key -> lane sharding (sml_serve_shard.h): (order [k], start [lanes + 1]); "
+      "lane l serves batch rows order[start[l]:start[l + 1]], in batch order",
+      py::arg("keys"), py::arg("lanes"));
   m.def("score_records",
         [](py::object keys, int partition, py::array_t<int64_t, py::array::c_style | py::array::forcecast> offsets,
            py::array_t<float, py::array::c_style | py::array::forcecast> scores,

@@ -808,7 +808,7 @@ int lstm_serve_select(const LstmServeArgs& args) {
 hipError_t lstm_serve_launch(const LstmServeArgs& args, hipStream_t stream) {
   const int which = lstm_serve_select(args);
   if (which == LSK_WIDE) return lstm_serve_wide_launch(args, stream);
-  if (!narrow_shape_ok(args)) return hipErrorInvalidValue;
+  if (!narrow_shape_ok(args) || args.lanes > 1) return hipErrorInvalidValue;   // lanes: the wide kernel only
   if (which == LSK_REF1) {
     auto k = args.L[0].act == ACT_RELU ? lstm_serve_ref1_kernel<1> : lstm_serve_ref1_kernel<0>;
     hipLaunchKernelGGL(k, dim3(1), dim3(64), 0, stream, args);

@@ -41,8 +41,38 @@
 //
 // Exit conditions every wave reaches: the host's stop flag or `idle` without a request
 // (decided by wave 0, broadcast through LDS at the next barrier).  Every branch around a
-// barrier is block-uniform: it depends only on kernel arguments and on values broadcast
-// through LDS (quit, the key's event count).
+// barrier is block-uniform: it depends only on kernel arguments (lanes among them) and on
+// values broadcast through LDS (quit, the key's event count).
+//
+// LANES.  The launch has a.lanes workgroups; workgroup i is lane i, a complete server of its
+// own: control block a.ctl[i] (its `done`, its `alive`), request and result rings a.req / a.res
+// + i * nslots, projection scratch a.wide_zx + i * rows * gmax.  The host sends key k to lane
+// k % lanes, so a key's window, count and forecast (indexed by key, shared arrays) are touched
+// by one lane only and in the key's event order: every result has the bits the one-lane server
+// gives.  Weight images, master weights, scale and shift are read-only and shared.  No lane
+// waits for another: there is no grid barrier and no lane reads what another lane computes,
+// so the launch is correct whether its workgroups run side by side or one after the other
+// (a lane that has not started yet only delays its own keys).  Waiting is what a resident
+// grid cannot afford: a workgroup spinning on a lane that the dispatcher has not placed yet
+// would never be released.
+//
+// LEAVING is collective and one-way.  With one idle timer per lane a quiet lane would leave
+// while a busy one keeps the launch (and the stream) alive, and the quiet lane's next event
+// would wait until the busy lane goes quiet too, because the host can only relaunch a
+// drained stream.  So the lanes share two words of lane 0's host-mapped control block, read
+// and written at system scope like `stop` (host memory: no per-XCD L2 holds a copy):
+//   active  s_memrealtime of the latest pick-up on any lane (stored by the lane that picks up);
+//   leave   the latch.  A lane whose own last event is idle_ticks old reads `active`; if the
+//           whole server has been idle that long, or the host's stop flag is up, it sets
+//           `leave`.  Every lane tests `leave` every 64 polls and after each event and leaves
+//           once it is set.  The host clears it before each launch, which it issues only on
+//           a drained stream, so no lane of the previous launch can still set it.
+// Races, all benign.  (1) A lane picks up an event as another sets the latch (the `active`
+// store still in flight, or the clocks of two XCDs a few ticks apart; the age is compared
+// signed): the lane finishes the event, stores its results and `done`, then leaves.  (2) An
+// event published after the latch, or to a lane that has left, stays in its ring; the host
+// sees the stream drain, relaunches, and every lane resumes at its own `done`.  (3) Two lanes
+// set the latch at once: same value.  With one lane the two words are not used at all.
 #include <type_traits>
 
 #include "sml_common.h"
@@ -54,7 +84,7 @@ namespace {
 
 using namespace serve_dev;
 
-constexpr int WNT = 1024;      // threads of the one workgroup
+constexpr int WNT = 1024;      // threads of a lane's workgroup
 constexpr int KEY_WORD = 31;   // request word carrying the car key
 constexpr int TB = 8;          // steps of the input projection per thread
 
@@ -185,7 +215,7 @@ __device__ __forceinline__ float wide_steps(const uint4* __restrict__ uimg, cons
   return h;
 }
 
-__global__ __launch_bounds__(WNT) void lstm_serve_wide_kernel(LstmServeArgs a, int rows, int S) {
+__global__ __launch_bounds__(WNT) void lstm_serve_wide_kernel(LstmServeArgs a, int rows, int S, int zx_lane) {
   extern __shared__ __attribute__((aligned(16))) uint16_t smem_w[];
   __shared__ __attribute__((aligned(16))) float s_part[4 * LSW_MAXW];   // partial sums [KS][4 up] / head [32][32]
   __shared__ __attribute__((aligned(16))) uint16_t s_hq[LSW_MAXW];      // h_{t-1}, bf16
@@ -195,6 +225,14 @@ __global__ __launch_bounds__(WNT) void lstm_serve_wide_kernel(LstmServeArgs a, i
   uint16_t* seq = smem_w;    // [rows][S]: the current layer's input / output sequence, bf16
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int D = a.D, T = a.T;
+  // this lane's control block, rings and scratch; stop / leave / active are lane 0's
+  const int ln = blockIdx.x;
+  const bool multi = a.lanes > 1;
+  ServeCtl* const ctl = a.ctl + ln;
+  ServeCtl* const ctl0 = a.ctl;
+  const ServeReq* const req = a.req + (size_t)ln * a.nslots;
+  ServeResult* const res = a.res + (size_t)ln * a.nslots;
+  float* const zx_mine = a.wide_zx + (size_t)ln * zx_lane;
   if (tid < 32) {
     s_sc[tid] = (tid < D && a.scale) ? a.scale[tid] : 1.f;
     s_sh[tid] = (tid < D && a.shift) ? a.shift[tid] : 0.f;
@@ -202,9 +240,9 @@ __global__ __launch_bounds__(WNT) void lstm_serve_wide_kernel(LstmServeArgs a, i
   if (tid < 8) s_ctl[tid] = 0;
   __syncthreads();
 
-  uint64_t tail = ld_sys(&a.ctl->done);
+  uint64_t tail = ld_sys(&ctl->done);
   uint64_t last = __builtin_amdgcn_s_memrealtime();
-  if (tid == 0) st_sys32(&a.ctl->alive, 1u);
+  if (tid == 0) st_sys32(&ctl->alive, 1u);
   for (;;) {
     // ---------------- waves 0..3 poll the next request slot as in lstm_serve.hip (staggered,
     // one synchronous cache-bypassing load per poll); the other waves wait at the barrier
@@ -214,7 +252,7 @@ __global__ __launch_bounds__(WNT) void lstm_serve_wide_kernel(LstmServeArgs a, i
       typedef __attribute__((address_space(3))) volatile int lds_vint;   // ds_* accesses, not flat
       lds_vint* seen = (lds_vint*)&s_ctl[3];
       lds_vint* quit_f = (lds_vint*)&s_ctl[0];
-      const uint64_t* wp = &a.req[slot].w[lane & 31];
+      const uint64_t* wp = &req[slot].w[lane & 31];
       if (wid == 1) __builtin_amdgcn_s_sleep(10);
       else if (wid == 2) __builtin_amdgcn_s_sleep(20);
       else if (wid == 3) __builtin_amdgcn_s_sleep(30);
@@ -229,13 +267,25 @@ __global__ __launch_bounds__(WNT) void lstm_serve_wide_kernel(LstmServeArgs a, i
             const uint64_t ts = __builtin_amdgcn_s_memrealtime();
             s_ctl[4] = (int)(uint32_t)ts;
             s_ctl[5] = (int)(uint32_t)(ts >> 32);
+            if (multi) st_sys(&ctl0->active, ts);   // the server is busy: no lane may call it idle
           }
           asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // row and key before the sequence
           if (lane == 0) *seen = (int)want;
           break;
         }
         if ((it & 63) == 63 && wid == 0) {   // exit conditions every wave reaches
-          if (ld_sys32(&a.ctl->stop) || __builtin_amdgcn_s_memrealtime() - last > a.idle_ticks) {
+          const uint64_t now = __builtin_amdgcn_s_memrealtime();
+          bool out = ld_sys32(&ctl0->stop) != 0;
+          if (!multi) {
+            out = out || now - last > a.idle_ticks;
+          } else {
+            out = out || ld_sys32(&ctl0->leave) != 0;
+            // this lane is idle: is the whole server?  (signed: clocks of two XCDs may differ)
+            if (!out && now - last > a.idle_ticks)
+              out = (int64_t)(now - ld_sys(&ctl0->active)) > (int64_t)a.idle_ticks;
+            if (out && lane == 0) st_sys32(&ctl0->leave, 1u);   // one-way: every lane follows
+          }
+          if (out) {
             if (lane == 0) *quit_f = 1;
             break;
           }
@@ -292,7 +342,7 @@ __global__ __launch_bounds__(WNT) void lstm_serve_wide_kernel(LstmServeArgs a, i
           const uint4* wimg = reinterpret_cast<const uint4*>(a.wide_w[li]);
           const uint4* uimg = reinterpret_cast<const uint4*>(a.wide_u[li]);
           const float* bias = a.wide_b[li];
-          float* zx = a.wide_zx;
+          float* zx = zx_mine;
           // ---- 1. input projection: thread = (column g, block of TB steps)
           const int ntb = (tcur + TB - 1) / TB;
           for (int item = tid; item < G * ntb; item += WNT) {
@@ -353,8 +403,11 @@ __global__ __launch_bounds__(WNT) void lstm_serve_wide_kernel(LstmServeArgs a, i
     const uint64_t t_comp = __builtin_amdgcn_s_memrealtime();
     const uint64_t t_seen = (uint64_t)(uint32_t)s_ctl[4] | ((uint64_t)(uint32_t)s_ctl[5] << 32);
     // ---------------- results (wave 0), the key's state, completion counter
+    // the latch, requested before the result stores so that its round trip hides behind them
+    uint32_t leave = 0;
+    if (multi && tid == 0) leave = ld_sys32(&ctl0->leave);
     if (wid == 0) {
-      ServeResult* r = a.res + slot;
+      ServeResult* r = res + slot;
       const float p = (full && lane < D) ? s_pred[lane] : 0.f;
       if (lane < D) {
         st_sys(&r->w[lane], tagged(want, p));
@@ -369,17 +422,18 @@ __global__ __launch_bounds__(WNT) void lstm_serve_wide_kernel(LstmServeArgs a, i
         st_sys(&r->w[kServeTLoad], tagged_u(want, (uint32_t)(t_rec - t_seen)));
         st_sys(&r->w[kServeTComp], tagged_u(want, (uint32_t)(t_comp - t_seen)));
         st_sys(&r->w[kServeTDone], tagged_u(want, (uint32_t)(__builtin_amdgcn_s_memrealtime() - t_seen)));
-        st_sys(&a.ctl->done, tail + 1);
+        st_sys(&ctl->done, tail + 1);
       }
     }
     tail += 1;
     last = __builtin_amdgcn_s_memrealtime();
     wait_stores();     // key state stored before the next event may read it
+    if (leave) s_ctl[0] = 1;   // reaches all 16 waves through LDS, as quit does
     __syncthreads();
   }
   __syncthreads();
   wait_stores();
-  if (tid == 0) st_sys32(&a.ctl->alive, 0u);
+  if (tid == 0) st_sys32(&ctl->alive, 0u);
 }
 
 }  // namespace
@@ -462,7 +516,8 @@ void lstm_serve_wide_image(const float* w, int K, int u, int Kp, int up, uint16_
 }
 
 hipError_t lstm_serve_wide_launch(const LstmServeArgs& args, hipStream_t stream) {
-  if (lstm_serve_wide_check(args)[0] || args.nslots < 64 || args.nkeys < 1 || !args.wide_zx)
+  if (lstm_serve_wide_check(args)[0] || args.nslots < 64 || args.nkeys < 1 || !args.wide_zx || args.lanes < 1 ||
+      args.lanes > LSW_MAXLANES)
     return hipErrorInvalidValue;
   int li = 0;
   for (int l = 0; l < args.nl; ++l)
@@ -478,7 +533,10 @@ hipError_t lstm_serve_wide_launch(const LstmServeArgs& args, hipStream_t stream)
                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
   }
-  hipLaunchKernelGGL(lstm_serve_wide_kernel, dim3(1), dim3(WNT), lds, stream, args, d.rows, d.stride);
+  // one launch, one workgroup per lane: lanes on streams of their own would share hardware
+  // queues, and a resident kernel queued behind another never starts (runtime/queues.h)
+  hipLaunchKernelGGL(lstm_serve_wide_kernel, dim3(args.lanes), dim3(WNT), lds, stream, args, d.rows, d.stride,
+                     d.rows * d.gmax);
   return hipGetLastError();
 }
 

@@ -1,5 +1,6 @@
 #include "serve.h"
 #include "queues.h"
+#include "sml_serve_shard.h"
 
 #include <chrono>
 #include <cstring>
@@ -26,20 +27,26 @@ inline void cpu_relax() {
 
 }  // namespace
 
-ServeRing::ServeRing(int device, int nslots, int D, double idle_seconds, int max_D)
-    : device_(device), nslots_(nslots), D_(D), idle_s_(idle_seconds) {
+ServeRing::ServeRing(int device, int nslots, int D, double idle_seconds, int max_D, int lanes)
+    : device_(device), nslots_(nslots), D_(D), lanes_(lanes), idle_s_(idle_seconds) {
   if (nslots < 64) throw std::invalid_argument("serve: nslots must be >= 64");
+  if (lanes < 1 || lanes > LSW_MAXLANES)
+    throw std::invalid_argument(std::string("serve: lanes must be 1..") + std::to_string((int)LSW_MAXLANES));
   if (max_D > 32) max_D = 32;   // a request slot holds 32 words
   if (D < 1 || D > max_D)
     throw std::invalid_argument(std::string("serve: rows must have 1..") + std::to_string(max_D) + " features");
+  head_.assign((size_t)lanes, 0);
+  complete_.assign((size_t)lanes, 0);
+  done0_.assign((size_t)lanes, 0);
   ck(hipSetDevice(device), "hipSetDevice");
   const unsigned fl = hipHostMallocMapped | hipHostMallocCoherent;
-  ck(hipHostMalloc((void**)&ctl_, sizeof(ServeCtl), fl), "hipHostMalloc ctl");
-  ck(hipHostMalloc((void**)&req_, sizeof(ServeReq) * (size_t)nslots, fl), "hipHostMalloc req");
-  ck(hipHostMalloc((void**)&res_, sizeof(ServeResult) * (size_t)nslots, fl), "hipHostMalloc res");
-  std::memset(ctl_, 0, sizeof(ServeCtl));
-  std::memset(req_, 0, sizeof(ServeReq) * (size_t)nslots);   // tag 0 = empty (tags start at 1)
-  std::memset(res_, 0, sizeof(ServeResult) * (size_t)nslots);
+  const size_t nall = (size_t)nslots * (size_t)lanes;
+  ck(hipHostMalloc((void**)&ctl_, sizeof(ServeCtl) * (size_t)lanes, fl), "hipHostMalloc ctl");
+  ck(hipHostMalloc((void**)&req_, sizeof(ServeReq) * nall, fl), "hipHostMalloc req");
+  ck(hipHostMalloc((void**)&res_, sizeof(ServeResult) * nall, fl), "hipHostMalloc res");
+  std::memset(ctl_, 0, sizeof(ServeCtl) * (size_t)lanes);
+  std::memset(req_, 0, sizeof(ServeReq) * nall);   // tag 0 = empty (tags start at 1)
+  std::memset(res_, 0, sizeof(ServeResult) * nall);
   ck(hipHostGetDevicePointer((void**)&ctl_d_, ctl_, 0), "device ptr ctl");
   ck(hipHostGetDevicePointer((void**)&req_d_, req_, 0), "device ptr req");
   ck(hipHostGetDevicePointer((void**)&res_d_, res_, 0), "device ptr res");
@@ -55,6 +62,8 @@ ServeRing::~ServeRing() {
 
 void ServeRing::launch() {
   ck(hipSetDevice(device_), "hipSetDevice");
+  // only ever called on a drained stream: no lane of an earlier launch can set the latch again
+  __atomic_store_n(&ctl_->leave, 0u, __ATOMIC_RELAXED);
   __atomic_store_n(&ctl_->stop, 0u, __ATOMIC_RELEASE);
   ck(launch_kernel(), "launch");
   ++launches_;
@@ -99,11 +108,35 @@ hipError_t AEServe::launch_kernel() {
                          idle_s_, stream_);
 }
 
+int LSTMServe::checked_lanes(int device, int lanes, const std::vector<LstmServeLayer>& layers, int D, int T) {
+  if (lanes == 1) return lanes;
+  if (lanes < 1 || lanes > LSW_MAXLANES)
+    throw std::invalid_argument(std::string("LSTMServe: lanes must be 1..") + std::to_string((int)LSW_MAXLANES));
+  if (!layers.empty() && layers.size() <= (size_t)LS_MAXLAYERS) {   // else refused below: 1..8 layers
+    LstmServeArgs a{};
+    a.nl = (int)layers.size();
+    for (size_t i = 0; i < layers.size(); ++i) a.L[i] = layers[i];
+    a.D = D;
+    a.T = T;
+    if (lstm_serve_select(a) != LSK_WIDE)
+      throw std::invalid_argument("LSTMServe: only the streamed-weight (wide) kernel runs on several lanes");
+  }
+  // a lane occupies a whole CU for as long as the server lives; the card also hosts the
+  // autoencoder scorer and training
+  int cus = 0;
+  ck(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device), "multiprocessor count");
+  if (lanes > cus / 2)
+    throw std::invalid_argument("LSTMServe: lanes must not exceed half the device's compute units (" +
+                                std::to_string(cus / 2) + " here)");
+  return lanes;
+}
+
 LSTMServe::LSTMServe(int device, int nslots, const std::vector<float>& weights,
                      const std::vector<LstmServeLayer>& layers, int D, int T, int nkeys,
                      const std::vector<float>& scale, const std::vector<float>& shift, float threshold,
-                     double idle_seconds)
-    : ServeRing(device, nslots, D, idle_seconds, 31) {   // request word 31 carries the car key
+                     double idle_seconds, int lanes)
+    // request word 31 carries the car key
+    : ServeRing(device, nslots, D, idle_seconds, 31, checked_lanes(device, lanes, layers, D, T)) {
   name_ = "LSTMServe";
   if (layers.empty() || layers.size() > (size_t)LS_MAXLAYERS) throw std::invalid_argument("LSTMServe: 1..8 layers");
   if (T < 1 || T > 64) throw std::invalid_argument("LSTMServe: look_back must be 1..64");
@@ -120,6 +153,7 @@ LSTMServe::LSTMServe(int device, int nslots, const std::vector<float>& weights,
     throw std::invalid_argument("LSTMServe: scale/shift size");
   LstmServeArgs& a = args_;
   a.nslots = nslots_;
+  a.lanes = lanes_;
   a.nw = (int)weights.size();
   a.nl = (int)layers.size();
   for (size_t i = 0; i < layers.size(); ++i) a.L[i] = layers[i];
@@ -135,6 +169,8 @@ LSTMServe::LSTMServe(int device, int nslots, const std::vector<float>& weights,
     if (why[0]) throw std::invalid_argument(std::string("LSTMServe: ") + why);
     if (lstm_serve_wide_lds_bytes(a) + 16 * 1024 > 160 * 1024)
       throw std::invalid_argument("LSTMServe: the window's sequences do not fit the forecaster's LDS");
+  } else if (lanes_ > 1) {   // repeated: SML_LSTM_SERVE_GENERIC may have changed between the two looks
+    throw std::invalid_argument("LSTMServe: only the streamed-weight (wide) kernel runs on several lanes");
   } else if (lstm_serve_lds_bytes((int)weights.size()) > 160 * 1024) {
     throw std::invalid_argument("LSTMServe: the weights do not fit the scorer's LDS");
   }
@@ -202,7 +238,8 @@ void LSTMServe::build_wide(const std::vector<float>& weights) {
     a.wide_b[i] = reinterpret_cast<const float*>(static_cast<unsigned char*>(wide_d_) + off[i][2]);
   }
   const LstmServeWideDims d = lstm_serve_wide_dims(a);
-  ck(hipMalloc((void**)&a.wide_zx, (size_t)d.rows * d.gmax * sizeof(float)), "hipMalloc projection scratch");
+  ck(hipMalloc((void**)&a.wide_zx, (size_t)lanes_ * d.rows * d.gmax * sizeof(float)),   // one scratch per lane
+     "hipMalloc projection scratch");
 }
 
 const char* LSTMServe::kernel() const {
@@ -214,6 +251,7 @@ void LSTMServe::reset_keys() {
   // the resident kernel reads and writes the key state: stop it first (flag + drain the
   // stream), so the memsets never queue behind a kernel that only leaves at its idle timeout
   stop();
+  mark_lane_events();
   ck(hipMemsetAsync(args_.hcount, 0, (size_t)args_.nkeys * sizeof(int), stream_), "memset counts");
   ck(hipMemsetAsync(args_.lastpred, 0, (size_t)args_.nkeys * args_.D * sizeof(float), stream_), "memset forecasts");
   ck(hipStreamSynchronize(stream_), "sync");
@@ -237,15 +275,16 @@ LSTMServe::~LSTMServe() {
 
 hipError_t LSTMServe::launch_kernel() { return lstm_serve_launch(args_, stream_); }
 
-uint64_t ServeRing::submit(const float* rows, int k, const uint32_t* keys) {
-  if (k <= 0) return head_;
+uint64_t ServeRing::submit(const float* rows, int k, const uint32_t* keys, int lane) {
+  uint64_t& head = head_[(size_t)lane];
+  if (k <= 0) return head;
   if (k > nslots_) throw std::invalid_argument("serve: more rows than slots");
   // back-pressure: never overwrite a slot whose event is not done
-  if (head_ + (uint64_t)k > (uint64_t)nslots_) wait_done(head_ + (uint64_t)k - (uint64_t)nslots_, 10.0);
-  const uint64_t first = head_;
+  if (head + (uint64_t)k > (uint64_t)nslots_) wait_done(head + (uint64_t)k - (uint64_t)nslots_, 10.0, lane);
+  const uint64_t first = head;
   for (int i = 0; i < k; ++i) {
     const uint64_t ev = first + (uint64_t)i;
-    ServeReq& dst = req_[ev % (uint64_t)nslots_];
+    ServeReq& dst = slot_req(ev, lane);
     const uint64_t tag = (uint64_t)(uint32_t)(ev + 1) << 32;
     const float* row = rows + (size_t)i * D_;
     for (int j = 0; j < D_; ++j) {   // 8-byte atomic stores: a word is never seen half-written
@@ -255,13 +294,13 @@ uint64_t ServeRing::submit(const float* rows, int k, const uint32_t* keys) {
     }
     if (keys) __atomic_store_n(&dst.w[31], tag | keys[i], __ATOMIC_RELAXED);
   }
-  head_ += k;
-  store_rel(&ctl_->head, head_);   // after the rows: the backlog path trusts rows below head
+  head += k;
+  store_rel(&ctl_[lane].head, head);   // after the rows: the backlog path trusts rows below head
   return first;
 }
 
-bool ServeRing::complete(uint64_t seq) const {
-  const ServeResult& r = res_[seq % (uint64_t)nslots_];
+bool ServeRing::complete(uint64_t seq, int lane) const {
+  const ServeResult& r = slot_res(seq, lane);
   const uint32_t tag = (uint32_t)(seq + 1);
   for (int i = kServeScore; i < kServeWords; ++i)
     if ((uint32_t)(__atomic_load_n(&r.w[i], __ATOMIC_RELAXED) >> 32) != tag) return false;
@@ -271,91 +310,156 @@ bool ServeRing::complete(uint64_t seq) const {
   return true;
 }
 
-uint32_t ServeRing::word(uint64_t seq, int i) const {
-  return (uint32_t)__atomic_load_n(&res_[seq % (uint64_t)nslots_].w[i], __ATOMIC_RELAXED);
+uint32_t ServeRing::word(uint64_t seq, int i, int lane) const {
+  return (uint32_t)__atomic_load_n(&slot_res(seq, lane).w[i], __ATOMIC_RELAXED);
 }
 
-float ServeRing::score(uint64_t seq) const {
-  const uint32_t b = word(seq, kServeScore);
+float ServeRing::score(uint64_t seq, int lane) const {
+  const uint32_t b = word(seq, kServeScore, lane);
   float f;
   std::memcpy(&f, &b, 4);
   return f;
 }
 
-void ServeRing::wait_done(uint64_t n, double timeout_s) {
+void ServeRing::mark_lane_events() {
+  for (int l = 0; l < lanes_; ++l) done0_[(size_t)l] = load_acq(&ctl_[l].done);
+}
+
+std::vector<int64_t> ServeRing::lane_events() const {
+  // the device stores `done` after the tagged result words that wait() polls, so a call can
+  // return a moment before the last `done` lands: events the host has already gathered count too
+  std::vector<int64_t> n((size_t)lanes_);
+  for (int l = 0; l < lanes_; ++l) {
+    const uint64_t done = std::max(load_acq(&ctl_[l].done), complete_[(size_t)l]);
+    n[(size_t)l] = (int64_t)(done - done0_[(size_t)l]);
+  }
+  return n;
+}
+
+void ServeRing::wait_done(uint64_t n, double timeout_s, int lane) {
   const auto t0 = std::chrono::steady_clock::now();
   uint32_t spins = 0;
-  while (load_acq(&ctl_->done) < n) {
+  const uint64_t* done = &ctl_[lane].done;
+  while (load_acq(done) < n) {
     cpu_relax();
     if ((++spins & 0x3ff) == 0) {
-      if (hipStreamQuery(stream_) == hipSuccess && load_acq(&ctl_->done) < n) launch();
+      if (hipStreamQuery(stream_) == hipSuccess && load_acq(done) < n) launch();
       const double el = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
       if (el > timeout_s) throw std::runtime_error(std::string(name_) + ": timed out waiting for free slots");
     }
   }
 }
 
-void ServeRing::wait(uint64_t seq_end, double timeout_s) {
+void ServeRing::wait(uint64_t seq_end, double timeout_s, int lane) {
   const auto t0 = std::chrono::steady_clock::now();
   uint32_t spins = 0;
-  uint64_t ev = complete_ < seq_end ? std::max<uint64_t>(complete_, seq_end > (uint64_t)nslots_ ?
-                                                                       seq_end - (uint64_t)nslots_ : 0)
-                                    : seq_end;
+  uint64_t& done = complete_[(size_t)lane];
+  uint64_t ev = done < seq_end ? std::max<uint64_t>(done, seq_end > (uint64_t)nslots_ ?
+                                                              seq_end - (uint64_t)nslots_ : 0)
+                               : seq_end;
   while (ev < seq_end) {
-    if (complete(ev)) {
+    if (complete(ev, lane)) {
       ++ev;
       continue;
     }
     cpu_relax();
     if ((++spins & 0x3ff) == 0) {
       // the kernel exits after idle_seconds without work, or may have raced its
-      // exit with our publish: relaunch it once it has really finished (it resumes
-      // at `done`, written after each event's result stores were issued)
-      if (hipStreamQuery(stream_) == hipSuccess && !complete(ev)) launch();
+      // exit with our publish: relaunch it once it has really finished (every lane
+      // resumes at its `done`, written after each event's result stores were issued)
+      if (hipStreamQuery(stream_) == hipSuccess && !complete(ev, lane)) launch();
       const double el = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
       if (el > timeout_s) throw std::runtime_error(std::string(name_) + ": timed out waiting for results");
     }
   }
-  complete_ = std::max(complete_, seq_end);
+  done = std::max(done, seq_end);
+}
+
+void ServeRing::copy_result(uint64_t seq, int lane, int row, float* scores, uint32_t* flags, float* recon) const {
+  if (scores) scores[row] = score(seq, lane);
+  if (flags) flags[row] = word(seq, kServeFlag, lane);
+  if (recon)
+    for (int j = 0; j < D_; ++j) {
+      const uint32_t b = word(seq, j, lane);
+      std::memcpy(&recon[(size_t)row * D_ + j], &b, 4);
+    }
 }
 
 void ServeRing::infer(const float* rows, int k, float* scores, uint32_t* flags, float* recon, double timeout_s,
                       const uint32_t* keys) {
+  if (lanes_ > 1) {
+    if (!keys) throw std::invalid_argument("serve: a ring with several lanes needs one key per row");
+    infer_lanes(rows, k, scores, flags, recon, timeout_s, keys);
+    return;
+  }
   int off = 0;
   while (off < k) {
     const int n = std::min(k - off, nslots_);
     const uint64_t first = submit(rows + (size_t)off * D_, n, keys ? keys + off : nullptr);
     wait(first + n, timeout_s);
-    for (int i = 0; i < n; ++i) {
-      const uint64_t ev = first + (uint64_t)i;
-      if (scores) scores[off + i] = score(ev);
-      if (flags) flags[off + i] = word(ev, kServeFlag);
-      if (recon)
-        for (int j = 0; j < D_; ++j) {
-          const uint32_t b = word(ev, j);
-          std::memcpy(&recon[(size_t)(off + i) * D_ + j], &b, 4);
-        }
-    }
+    for (int i = 0; i < n; ++i) copy_result(first + (uint64_t)i, 0, off + i, scores, flags, recon);
     off += n;
   }
 }
 
+void ServeRing::infer_lanes(const float* rows, int k, float* scores, uint32_t* flags, float* recon,
+                            double timeout_s, const uint32_t* keys) {
+  // lane l's j-th event of this batch: sequence number base[l] + j, batch row order[start[l] + j].
+  // Every earlier call gathered all it published, so base[l] is also the lane's oldest
+  // event whose result slot is still needed.
+  const ServeLanePartition part = serve_lane_partition(keys, k, lanes_);
+  const std::vector<uint64_t> base(head_);
+  std::vector<int> pub((size_t)lanes_, 0), got((size_t)lanes_, 0);
+  // the lane's oldest ungathered event: wait for it (block), or take it only if it has landed
+  auto gather = [&](int l, bool block) {
+    const uint64_t ev = base[(size_t)l] + (uint64_t)got[(size_t)l];
+    if (block)
+      wait(ev + 1, timeout_s, l);
+    else if (!complete(ev, l))
+      return false;
+    copy_result(ev, l, part.order[(size_t)(part.start[(size_t)l] + got[(size_t)l])], scores, flags, recon);
+    ++got[(size_t)l];
+    // the lane's complete prefix moves with every gathered event, on either path: once ev is
+    // gathered its slot may be published again (event ev + nslots), and a later wait() that
+    // started below ev + 1 would look for ev's tag in a slot that no longer carries it
+    complete_[(size_t)l] = std::max(complete_[(size_t)l], ev + 1);
+    return true;
+  };
+  for (int i = 0; i < k; ++i) {   // one walk in batch order: a lane sees its keys' events in order
+    const int l = serve_lane_of(keys[i], lanes_);
+    if (pub[(size_t)l] - got[(size_t)l] == nslots_) {
+      // this lane's ring is full (its result slots too): block on its oldest event, the one
+      // the device reaches first, then take whatever else has landed.  The other lanes
+      // already hold their share of the rows walked so far and keep draining meanwhile.
+      gather(l, true);
+      while (got[(size_t)l] < pub[(size_t)l] && gather(l, false)) {
+      }
+    }
+    submit(rows + (size_t)i * D_, 1, keys + i, l);
+    ++pub[(size_t)l];
+  }
+  for (int l = 0; l < lanes_; ++l)
+    while (got[(size_t)l] < pub[(size_t)l]) gather(l, true);
+}
+
 std::vector<int64_t> ServeRing::latency_run(const float* rows, int n, int64_t gap_ns, std::vector<int64_t>* dev_ns,
                                             const uint32_t* keys) {
+  if (lanes_ > 1 && !keys) throw std::invalid_argument("serve: a ring with several lanes needs one key per row");
   std::vector<int64_t> lat(n);
   if (dev_ns) dev_ns->assign(n, 0);
   auto next = std::chrono::steady_clock::now();
   for (int i = 0; i < n; ++i) {
     while (std::chrono::steady_clock::now() < next) cpu_relax();
+    const int l = lanes_ > 1 ? serve_lane_of(keys[i], lanes_) : 0;   // the lane that runs the event
     const auto t0 = std::chrono::steady_clock::now();
-    const uint64_t s = submit(rows + (size_t)i * D_, 1, keys ? keys + i : nullptr);
-    wait(s + 1, 10.0);
+    const uint64_t s = submit(rows + (size_t)i * D_, 1, keys ? keys + i : nullptr, l);
+    wait(s + 1, 10.0, l);
     const auto t1 = std::chrono::steady_clock::now();
     lat[i] = std::chrono::duration_cast<std::chrono::nanoseconds>(t1 - t0).count();
     if (dev_ns) {
       // 100 MHz ticks -> ns, packed: [total | load | compute] in three 21-bit fields (ns / 10)
-      const int64_t tot = word(s, kServeTDone), ld = word(s, kServeTLoad),
-                    cp = (int64_t)word(s, kServeTComp) - (int64_t)word(s, kServeTLoad);
+      const int64_t tot = word(s, kServeTDone, l), ld = word(s, kServeTLoad, l),
+                    cp = (int64_t)word(s, kServeTComp, l) - (int64_t)word(s, kServeTLoad, l);
       (*dev_ns)[i] = (std::min<int64_t>(tot, 0x1fffff) << 42) | (std::min<int64_t>(ld, 0x1fffff) << 21) |
                      std::min<int64_t>(cp, 0x1fffff);
     }
@@ -364,13 +468,15 @@ std::vector<int64_t> ServeRing::latency_run(const float* rows, int n, int64_t ga
   return lat;
 }
 
-std::vector<uint64_t> ServeRing::debug_state(uint64_t seq) const {
-  std::vector<uint64_t> v = {__atomic_load_n(&ctl_->head, __ATOMIC_ACQUIRE), __atomic_load_n(&ctl_->done, __ATOMIC_ACQUIRE),
-                             __atomic_load_n(&ctl_->stop, __ATOMIC_ACQUIRE), __atomic_load_n(&ctl_->alive, __ATOMIC_ACQUIRE),
+std::vector<uint64_t> ServeRing::debug_state(uint64_t seq, int lane) const {
+  if (lane < 0 || lane >= lanes_) throw std::out_of_range("serve: lane outside [0, lanes)");
+  const ServeCtl& c = ctl_[lane];
+  std::vector<uint64_t> v = {__atomic_load_n(&c.head, __ATOMIC_ACQUIRE), __atomic_load_n(&c.done, __ATOMIC_ACQUIRE),
+                             __atomic_load_n(&ctl_->stop, __ATOMIC_ACQUIRE), __atomic_load_n(&c.alive, __ATOMIC_ACQUIRE),
                              launches_, hipStreamQuery(stream_) == hipSuccess ? 1u : 0u};
-  const ServeResult& r = res_[seq % (uint64_t)nslots_];
+  const ServeResult& r = slot_res(seq, lane);
   for (size_t i = 0; i < sizeof(ServeResult) / 8; ++i) v.push_back(__atomic_load_n(&r.w[i], __ATOMIC_ACQUIRE));
-  const ServeReq& q = req_[seq % (uint64_t)nslots_];
+  const ServeReq& q = slot_req(seq, lane);
   for (int i = 0; i < 32; ++i) v.push_back(__atomic_load_n(&q.w[i], __ATOMIC_ACQUIRE));
   return v;
 }

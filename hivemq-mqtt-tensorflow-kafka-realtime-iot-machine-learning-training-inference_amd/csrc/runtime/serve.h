@@ -8,6 +8,12 @@
 // result words in host memory.  `done` is only a back-pressure / restart hint.  If
 // the kernel exited (idle timeout or a race with its exit), wait() relaunches it; it
 // resumes at `done`.
+//
+// A ring may have several LANES (the wide LSTM forecaster): lane i has its own control block,
+// request ring and result ring (ctl_[i], req_ / res_ + i * nslots, one allocation each) and
+// its own sequence numbers; one launch on the one persistent stream runs a workgroup per
+// lane.  infer() sends key k to lane k % lanes (sml_serve_shard.h) and gathers the results
+// back into batch order.  stop and the leave latch are lane 0's words and act on every lane.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -25,24 +31,28 @@ class ServeRing {
  public:
   // max_D: widest row the subclass's kernel takes (<= 32 request words; 31 when word 31
   // carries a key)
-  ServeRing(int device, int nslots, int D, double idle_seconds, int max_D);
+  // nslots: slots per lane
+  ServeRing(int device, int nslots, int D, double idle_seconds, int max_D, int lanes = 1);
   virtual ~ServeRing();
   ServeRing(const ServeRing&) = delete;
   ServeRing& operator=(const ServeRing&) = delete;
 
-  // Publish k rows of D floats (keys: optional per-row uint32 in request word 31);
-  // returns the sequence number of the first one.
-  uint64_t submit(const float* rows, int k, const uint32_t* keys = nullptr);
-  // Block until the results of the events in [seq_end - nslots, seq_end) have landed
+  // Publish k rows of D floats to one lane (keys: optional per-row uint32 in request word
+  // 31); returns the lane's sequence number of the first one.
+  uint64_t submit(const float* rows, int k, const uint32_t* keys = nullptr, int lane = 0);
+  // Block until the results of the lane's events in [seq_end - nslots, seq_end) have landed
   // (throws after timeout_s).
-  void wait(uint64_t seq_end, double timeout_s);
-  const ServeResult& result(uint64_t seq) const { return res_[seq % (uint64_t)nslots_]; }
+  void wait(uint64_t seq_end, double timeout_s, int lane = 0);
+  const ServeResult& result(uint64_t seq, int lane = 0) const { return slot_res(seq, lane); }
   // all tagged words of event seq's result have landed
-  bool complete(uint64_t seq) const;
+  bool complete(uint64_t seq, int lane = 0) const;
   // payload of result word i of event seq (call after complete())
-  uint32_t word(uint64_t seq, int i) const;
-  float score(uint64_t seq) const;
-  // submit + wait + copy scores / flags (/ recon) for k rows.
+  uint32_t word(uint64_t seq, int i, int lane = 0) const;
+  float score(uint64_t seq, int lane = 0) const;
+  // submit + wait + copy scores / flags (/ recon) for k rows.  With several lanes (keys
+  // required) each row goes to its key's lane, in batch order within the lane; back-pressure
+  // is per lane: when a lane's ring is full the host gathers that lane's oldest results
+  // (the other lanes keep draining on the device) before it publishes more.
   void infer(const float* rows, int k, float* scores, uint32_t* flags, float* recon, double timeout_s,
              const uint32_t* keys = nullptr);
   // Per-event latency (ns) of n events submitted one at a time, spaced by gap_ns.
@@ -51,29 +61,47 @@ class ServeRing {
                                    const uint32_t* keys = nullptr);
   void stop();
   int D() const { return D_; }
-  // debugging: {head, done, stop, alive, launches, stream idle (1) / busy (0)} then the raw
-  // result words and request words of event `seq`'s slot
-  std::vector<uint64_t> debug_state(uint64_t seq) const;
+  int lanes() const { return lanes_; }
+  int nslots() const { return nslots_; }
+  // debugging: {head, done, stop, alive, launches, stream idle (1) / busy (0)} of a lane, then
+  // the raw result words and request words of its event `seq`'s slot
+  std::vector<uint64_t> debug_state(uint64_t seq, int lane = 0) const;
   uint64_t launches() const { return launches_; }
+  // events each lane completed since construction or mark_lane_events(), from the lanes'
+  // completion counters
+  std::vector<int64_t> lane_events() const;
 
  protected:
   virtual hipError_t launch_kernel() = 0;
   void launch();
   // back-pressure: block until the device consumed every event < n (its request slot is free)
-  void wait_done(uint64_t n, double timeout_s);
-  int device_, nslots_, D_;
+  void wait_done(uint64_t n, double timeout_s, int lane = 0);
+  void mark_lane_events();   // lane_events() counts from here
+  int device_, nslots_, D_, lanes_;
   double idle_s_;
-  ServeCtl* ctl_ = nullptr;
-  ServeReq* req_ = nullptr;
-  ServeResult* res_ = nullptr;
+  ServeCtl* ctl_ = nullptr;      // [lanes]
+  ServeReq* req_ = nullptr;      // [lanes][nslots]
+  ServeResult* res_ = nullptr;   // [lanes][nslots]
   ServeCtl* ctl_d_ = nullptr;
   ServeReq* req_d_ = nullptr;
   ServeResult* res_d_ = nullptr;
   hipStream_t stream_ = nullptr;
-  uint64_t head_ = 0;
+  std::vector<uint64_t> head_;       // per lane: events published
+  std::vector<uint64_t> complete_;   // per lane: events known complete (prefix)
+  std::vector<uint64_t> done0_;      // per lane: `done` at mark_lane_events()
   uint64_t launches_ = 0;
-  uint64_t complete_ = 0;   // events known complete (prefix)
   const char* name_ = "serve";
+
+ private:
+  ServeReq& slot_req(uint64_t seq, int lane) const {
+    return req_[(size_t)lane * (size_t)nslots_ + (size_t)(seq % (uint64_t)nslots_)];
+  }
+  ServeResult& slot_res(uint64_t seq, int lane) const {
+    return res_[(size_t)lane * (size_t)nslots_ + (size_t)(seq % (uint64_t)nslots_)];
+  }
+  void copy_result(uint64_t seq, int lane, int row, float* scores, uint32_t* flags, float* recon) const;
+  void infer_lanes(const float* rows, int k, float* scores, uint32_t* flags, float* recon, double timeout_s,
+                   const uint32_t* keys);
 };
 
 // Dense autoencoder scorer (ae_serve.hip): reconstruction + MSE anomaly score per event.
@@ -98,10 +126,12 @@ class AEServe : public ServeRing {
 // event is scored against the key's previous forecast and a new forecast is emitted.
 class LSTMServe : public ServeRing {
  public:
-  // layers: LstmServeLayer descriptors (offsets into weights); keys in [0, nkeys)
+  // layers: LstmServeLayer descriptors (offsets into weights); keys in [0, nkeys); lanes:
+  // resident workgroups (1..LSW_MAXLANES, at most half the device's CUs; more than one only
+  // for stacks that take the wide kernel), key k is served by lane k % lanes
   LSTMServe(int device, int nslots, const std::vector<float>& weights, const std::vector<LstmServeLayer>& layers,
             int D, int T, int nkeys, const std::vector<float>& scale, const std::vector<float>& shift, float threshold,
-            double idle_seconds);
+            double idle_seconds, int lanes = 1);
   ~LSTMServe() override;
   int nkeys() const { return args_.nkeys; }
   // forget every key's window and forecast: stops the resident kernel, zeroes the key state
@@ -114,8 +144,10 @@ class LSTMServe : public ServeRing {
   hipError_t launch_kernel() override;
 
  private:
+  // every limit on `lanes`, before the base class allocates the rings; returns lanes
+  static int checked_lanes(int device, int lanes, const std::vector<LstmServeLayer>& layers, int D, int T);
   // wide stacks: bf16 images of every LSTM layer's W and U, padded biases (one allocation)
-  // and the input projection's scratch, built once before the resident kernel starts
+  // and each lane's input projection scratch, built once before the resident kernel starts
   void build_wide(const std::vector<float>& weights);
   LstmServeArgs args_{};
   int kernel_ = LSK_GENERIC;

@@ -1455,7 +1455,7 @@ struct LSTMServePy : ServePy {
   int64_t nk = 0;
   LSTMServePy(int device, int nslots, py::array_t<float, py::array::c_style | py::array::forcecast> weights,
               std::vector<std::vector<int>> layers, int D, int T, int nkeys, py::object scale, py::object shift,
-              double threshold, double idle_seconds) {
+              double threshold, double idle_seconds, int lanes) {
     std::vector<float> w(weights.data(), weights.data() + weights.size());
     std::vector<sml::LstmServeLayer> L;
     for (const auto& t : layers) {
@@ -1470,7 +1470,8 @@ struct LSTMServePy : ServePy {
       sh.assign(b.data(), b.data() + b.size());
     }
     c10::hip::HIPGuard guard(device);
-    s = std::make_unique<sml::LSTMServe>(device, nslots, w, L, D, T, nkeys, sc, sh, (float)threshold, idle_seconds);
+    s = std::make_unique<sml::LSTMServe>(device, nslots, w, L, D, T, nkeys, sc, sh, (float)threshold, idle_seconds,
+                                         lanes);
     nk = nkeys;
   }
   int64_t nkeys() const override { return nk; }
@@ -1648,7 +1649,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("lstm_fused_supported", &sml::lstm_fused_supported, "whether (U, IN) has a fused LSTM kernel", py::arg("U"),
         py::arg("IN"));
   py::class_<ServePy>(m, "AEServe", "persistent per-event autoencoder scorer over host-mapped rings")
-      .def("debug_state", [](ServePy& p, uint64_t seq) { return p.s->debug_state(seq); }, py::arg("seq"))
+      .def("debug_state", [](ServePy& p, uint64_t seq, int lane) { return p.s->debug_state(seq, lane); },
+           py::arg("seq"), py::arg("lane") = 0)
       .def(py::init<int, int, py::array_t<float, py::array::c_style | py::array::forcecast>, std::vector<int>,
                     std::vector<int>, py::object, py::object, double, double>(),
            py::arg("device"), py::arg("nslots"), py::arg("weights"), py::arg("dims"), py::arg("acts"),
@@ -1663,10 +1665,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   py::class_<LSTMServePy, ServePy>(m, "LSTMServe",
                                    "persistent per-event LSTM forecaster: per-key windows on the device")
       .def(py::init<int, int, py::array_t<float, py::array::c_style | py::array::forcecast>,
-                    std::vector<std::vector<int>>, int, int, int, py::object, py::object, double, double>(),
+                    std::vector<std::vector<int>>, int, int, int, py::object, py::object, double, double, int>(),
            py::arg("device"), py::arg("nslots"), py::arg("weights"), py::arg("layers"), py::arg("D"), py::arg("T"),
            py::arg("nkeys"), py::arg("scale") = py::none(), py::arg("shift") = py::none(),
-           py::arg("threshold") = 5.0, py::arg("idle_seconds") = 2.0)
+           py::arg("threshold") = 5.0, py::arg("idle_seconds") = 2.0, py::arg("lanes") = 1)
       .def("reset_keys", [](LSTMServePy& p) {
         p.s->stop();   // the kernel must not run while its state is cleared
         static_cast<sml::LSTMServe*>(p.s.get())->reset_keys();
@@ -1676,7 +1678,19 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
                                return std::string(static_cast<sml::LSTMServe*>(p.s.get())->kernel());
                              },
                              "the kernel lstm_serve_launch chose: ref1 | pipe | generic | wide")
-      .def_property_readonly("nkeys", [](LSTMServePy& p) { return p.nk; });
+      .def_property_readonly("nkeys", [](LSTMServePy& p) { return p.nk; })
+      .def_property_readonly("lanes", [](LSTMServePy& p) { return p.s->lanes(); },
+                             "resident workgroups; key k is served by lane k % lanes")
+      .def_property_readonly("nslots", [](LSTMServePy& p) { return p.s->nslots(); }, "slots per lane")
+      .def_property_readonly(
+          "lane_events",
+          [](LSTMServePy& p) {
+            const std::vector<int64_t> n = p.s->lane_events();
+            py::array_t<int64_t> out((ssize_t)n.size());
+            std::copy(n.begin(), n.end(), out.mutable_data());
+            return out;
+          },
+          "events each lane completed since construction or reset_keys (its completion counter)");
   m.def("lstm_head", &lstm_head, "fused LSTM Dense head: forward, MSE + accuracy, dW / db, dh (one pass + fold)",
         py::arg("h"), py::arg("W"), py::arg("b"), py::arg("y"), py::arg("gscale"), py::arg("grad"), py::arg("map"),
         py::arg("acc"), py::arg("out") = py::none(), py::arg("div0") = 1.0, py::arg("div1") = 1.0,

@@ -110,19 +110,28 @@ class LSTMScoringServer:
     ``"ref1"``, ``"pipe"`` or ``"generic"``, fp32 throughout); anything wider, up to
     ``MAX_WIDTH`` units or inputs per layer, runs on the streamed-weight kernel (``"wide"``:
     bf16 weight images, bf16-rounded x and h, fp32 everywhere else; widths zero-padded to
-    ``WIDE_TILE``)."""
+    ``WIDE_TILE``).
+
+    ``lanes`` (wide stacks only, up to ``MAX_LANES``): that many resident workgroups, each a
+    complete one-event-at-a-time server with ``slots`` request / result slots of its own; key
+    ``k`` is served by lane ``k % lanes``, so a key's events stay in order on one lane and
+    every result has the bits the one-lane server gives, while events of different lanes
+    run side by side."""
 
     MAX_WIDTH = 512      # LSTM units, layer inputs, head inputs
     MAX_FEATURES = 31    # request word 31 carries the key
     MAX_LOOK_BACK = 64
     MAX_LAYERS = 8
     WIDE_TILE = 32       # the wide kernel pads every width to a multiple of this
+    MAX_LANES = 32       # resident workgroups of the wide kernel (the device also caps it: half its CUs)
 
     @staticmethod
-    def supports(model) -> Tuple[bool, str]:
-        """(True, "") if the forecaster can serve ``model``, else (False, the limit it
-        exceeds).  Mirrors the checks of ``LSTMServe``'s constructor; needs no device."""
+    def supports(model, lanes: int = 1) -> Tuple[bool, str]:
+        """(True, "") if the forecaster can serve ``model`` on ``lanes`` lanes, else (False, the
+        limit it exceeds).  Mirrors the checks of ``LSTMServe``'s constructor; needs no device."""
         S = LSTMScoringServer
+        if not 1 <= int(lanes) <= S.MAX_LANES:
+            return False, f"lanes must be 1..{S.MAX_LANES}"
         if not 1 <= int(model.features) <= S.MAX_FEATURES:
             return False, f"rows must have 1..{S.MAX_FEATURES} features (request word 31 carries the key)"
         if not 1 <= int(model.look_back) <= S.MAX_LOOK_BACK:
@@ -152,14 +161,17 @@ class LSTMScoringServer:
             return False, "the stack needs an LSTM layer"
         if layers[-1]["kind"] != "dense" or layers[-1]["units"] != int(model.features):
             return False, "the stack must end in a Dense head with one output per feature"
+        if int(lanes) > 1 and not wide:
+            return False, "only the streamed-weight (wide) kernel runs on several lanes"
         return True, ""
 
     def __init__(self, model, nkeys: int = 100_000, threshold: float = 5.0, slots: int = 4096,
-                 idle_seconds: float = 2.0, normalizer: Optional[str] = "cardata", device: Optional[torch.device] = None):
+                 idle_seconds: float = 2.0, normalizer: Optional[str] = "cardata", device: Optional[torch.device] = None,
+                 lanes: int = 1):
         dev = torch.device(device) if device is not None else model.device
         if dev.type != "cuda":
             raise RuntimeError("LSTMScoringServer needs a ROCm device (use LSTMPredictor.predict on CPU)")
-        ok, why = self.supports(model)
+        ok, why = self.supports(model, lanes=lanes)
         if not ok:
             raise ValueError(f"LSTMScoringServer cannot serve this model: {why}")
         flat, table = lstm_layer_table(model)
@@ -173,7 +185,7 @@ class LSTMScoringServer:
         self.threshold = float(threshold)
         self._s = load_c().LSTMServe(dev.index if dev.index is not None else torch.cuda.current_device(), int(slots),
                                      flat, [list(t) for t in table], self.D, self.T, self.nkeys, sc, sh,
-                                     float(threshold), float(idle_seconds))
+                                     float(threshold), float(idle_seconds), int(lanes))
 
     def forecast(self, rows, keys) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
         """Events in order -> (forecast of each key's next event [k, D] (zeros until the key has
@@ -198,6 +210,21 @@ class LSTMScoringServer:
     def reset(self) -> None:
         """Forget every key's window and forecast."""
         self._s.reset_keys()
+
+    @property
+    def lanes(self) -> int:
+        return int(self._s.lanes)
+
+    @property
+    def slots(self) -> int:
+        """Request / result slots of each lane."""
+        return int(self._s.nslots)
+
+    @property
+    def lane_events(self) -> np.ndarray:
+        """int64 [lanes]: events each lane completed since construction or the last ``reset()``
+        (read from the lanes' completion counters)."""
+        return np.asarray(self._s.lane_events, np.int64)
 
     @property
     def kernel(self) -> str:
