@@ -20,7 +20,9 @@ only (cardata-v3.py:46) and writes reconstructions (cardata-v3.py:243-249). Here
 (:class:`streamml.kafka.scoreloop.LowLatencyScorer`): long-poll fetch -> Avro decode (or,
 ``--source-format json``, the bridge's JSON events) -> the persistent GPU scorer
 (:class:`streamml.ops.serve.ScoringServer`; ``--model lstm``: the per-car forecaster
-:class:`~streamml.ops.serve.LSTMScoringServer`, car key -> device slot in C++), no launch
+:class:`~streamml.ops.serve.LSTMScoringServer`, car key -> device slot in C++; ``--model dense``:
+:class:`~streamml.ops.serve.DenseScoringServer` for a Dense autoencoder of any depth, on both
+the chunked and the low-latency path), no launch
 per event -> the same result records formatted in C++ -> one produce per fetch -> commit.
 
 Replica identity comes from ``--replica-index/--replicas``, else torchrun's
@@ -94,9 +96,11 @@ def _flags(p) -> None:
                    help="--low-latency: CPUs for the loop thread, e.g. '4' or '4-7,12', or 'auto' (one core of "
                         "an L3 domain, a different one per replica); a loopback hop across core "
                         "complexes costs microseconds (profiles/r04 SUMMARY §7)")
-    p.add_argument("--model", choices=["autoencoder", "lstm"], default="autoencoder",
+    p.add_argument("--model", choices=["autoencoder", "lstm", "dense"], default="autoencoder",
                    help="lstm: per-car forecaster (look_back events per car on the device, each event "
-                        "scored against the car's previous forecast; lstm_serve.hip)")
+                        "scored against the car's previous forecast; lstm_serve.hip).  dense: a Dense "
+                        "autoencoder of any depth (1..8 layers up to 512 wide, saved from nn.Sequential / "
+                        "nn.Model) on the persistent scorer of dense_serve.hip")
     p.add_argument("--max-keys", type=int, default=200_000, help="--model lstm: car keys held on the device")
     p.add_argument("--lanes", type=int, default=1,
                    help="--model lstm: resident workgroups of the forecaster; car key k is served by lane "
@@ -137,6 +141,20 @@ def _require_servable(model, lanes: int = 1) -> None:
         raise SystemExit(f"--model lstm: the persistent forecaster cannot serve this model: {why}")
 
 
+def _require_dense_servable(model) -> None:
+    """``--model dense``: exit naming the limit the persistent Dense scorer cannot serve, the
+    missing ROCm device, or the feature count the cardata normaliser needs."""
+    from ..ops.serve import DenseScoringServer
+    ok, why = DenseScoringServer.supports(model)
+    if not ok:
+        raise SystemExit(f"--model dense: the persistent scorer cannot serve this model: {why}")
+    if model.device.type != "cuda":
+        raise SystemExit("--model dense serving needs a ROCm device (the persistent scorer)")
+    features = int(model._input_shape()[0])
+    if features != 18:
+        raise SystemExit(f"--model dense: the cardata normaliser needs 18 input features, the model has {features}")
+
+
 def _serve_low_latency(ns, servers, cfg, model, mine, result_parts, summary, rank: int = 0,
                        hash_ranges=None) -> int:
     """One C++ loop per replica over the resident scorer: the autoencoder's, or -- ``--model
@@ -144,14 +162,20 @@ def _serve_low_latency(ns, servers, cfg, model, mine, result_parts, summary, ran
     (cardata-v2.py:220-273 streams one LSTM prediction per event)."""
     from ..kafka.scoreloop import LowLatencyScorer
     from ..obs.metrics import ENGINE
-    from ..ops.serve import LSTMScoringServer, ScoringServer
+    from ..ops.serve import DenseScoringServer, LSTMScoringServer, ScoringServer
 
+    if ns.model == "dense":
+        _require_dense_servable(model)
     if model.device.type != "cuda":
         raise SystemExit("--low-latency needs a ROCm device (the persistent scorer)")
     if ns.model == "lstm":
         _require_servable(model, ns.lanes)
-    scorer = (LSTMScoringServer(model, nkeys=ns.max_keys, threshold=ns.threshold, lanes=ns.lanes)
-              if ns.model == "lstm" else ScoringServer(model, threshold=ns.threshold))
+    if ns.model == "lstm":
+        scorer = LSTMScoringServer(model, nkeys=ns.max_keys, threshold=ns.threshold, lanes=ns.lanes)
+    elif ns.model == "dense":
+        scorer = DenseScoringServer(model, threshold=ns.threshold, normalizer="cardata")
+    else:
+        scorer = ScoringServer(model, threshold=ns.threshold)
     with scorer as srv:
         starts = None
         if ns.from_beginning:
@@ -175,6 +199,8 @@ def _serve_low_latency(ns, servers, cfg, model, mine, result_parts, summary, ran
     ENGINE.anomaly_events.inc(st["anomalies"], model=model.name)
     if ns.model == "lstm":
         summary.update(model="lstm", keys=st["keys"])
+    elif ns.model == "dense":
+        summary.update(model="dense")
     summary.update(events=st["events"], anomalies=st["anomalies"], skipped=st["skipped"], foreign=st["foreign"],
                    keys_dropped=st["keys_dropped"],
                    events_per_s=st["events"] / st["wall_s"] if st["wall_s"] > 0 else 0.0, low_latency=True,
@@ -212,6 +238,10 @@ def main(argv: Sequence[str]) -> int:
     if ns.model == "lstm":
         from ..models.lstm import LSTMPredictor
         model = LSTMPredictor.load(path, device=device)
+    elif ns.model == "dense":
+        from ..nn.model import load_model as load_nn_model
+        model = load_nn_model(path, device=device, compile=False)
+        _require_dense_servable(model)
     else:
         model = load_model(path, device=device, input_normalizer="cardata")
     if ns.metrics_port and rank == 0:
@@ -247,7 +277,11 @@ def main(argv: Sequence[str]) -> int:
     if ns.low_latency:
         return _serve_low_latency(ns, servers, cfg, model, mine, result_parts, summary, rank,
                                   [(lo, hi) for _, lo, hi in shares])
-    forecaster, key_ids = None, {}
+    forecaster, key_ids, dense_srv = None, {}, None
+    if ns.model == "dense":
+        from ..ops.serve import DenseScoringServer
+        dense_srv = DenseScoringServer(model, threshold=ns.threshold, normalizer="cardata",
+                                       slots=max(64, min(ns.max_batch, 4096)))
     if ns.model == "lstm":
         if model.device.type != "cuda":
             raise SystemExit("--model lstm serving needs a ROCm device (the persistent forecaster)")
@@ -290,6 +324,11 @@ def main(argv: Sequence[str]) -> int:
             flags = fl == 1               # 2 = the car has no forecast yet (score NaN)
             if ns.emit == "both":
                 recon = pred
+        elif dense_srv is not None:
+            if ns.emit == "both":
+                scores, flags, recon = dense_srv.infer(chunk.x)
+            else:
+                scores, flags = dense_srv.score(chunk.x)
         elif ns.emit == "both":
             recon, scores = model.reconstruct_and_score(chunk.x, batch_size=ns.max_batch)
             flags = scores > ns.threshold
@@ -319,6 +358,9 @@ def main(argv: Sequence[str]) -> int:
         forecaster.close()
         summary["model"] = "lstm"
         summary["keys"] = len(key_ids)
+    if dense_srv is not None:
+        summary.update(model="dense", kernel=dense_srv.kernel)
+        dense_srv.close()
     wall = time.perf_counter() - t0
     summary["events_per_s"] = summary["events"] / wall if wall > 0 else 0.0
     print(json.dumps(summary), flush=True)

@@ -108,6 +108,78 @@ hipError_t AEServe::launch_kernel() {
                          idle_s_, stream_);
 }
 
+int DenseServe::checked_D(const std::vector<float>& image, const std::vector<DenseServeLayer>& layers, int D,
+                          const std::vector<float>& scale, const std::vector<float>& shift) {
+  if (layers.empty() || layers.size() > (size_t)DSV_MAXLAYERS)
+    throw std::invalid_argument("DenseServe: the stack must have 1..8 Dense layers");
+  const char* why = dense_serve_check(layers.data(), (int)layers.size(), D, (int64_t)image.size());
+  if (why[0]) throw std::invalid_argument(std::string("DenseServe: ") + why);
+  if (!scale.empty() && ((int)scale.size() != D || (int)shift.size() != D))
+    throw std::invalid_argument("DenseServe: scale/shift size");
+  return D;
+}
+
+DenseServe::DenseServe(int device, int nslots, const std::vector<float>& image,
+                       const std::vector<DenseServeLayer>& layers, int D, const std::vector<float>& scale,
+                       const std::vector<float>& shift, float threshold, double idle_seconds)
+    : ServeRing(device, nslots, checked_D(image, layers, D, scale, shift), idle_seconds, 32) {   // no key word: all 32
+  name_ = "DenseServe";
+  DenseServeArgs& a = args_;
+  a.nslots = nslots_;
+  a.D = D;
+  a.nl = (int)layers.size();
+  for (size_t i = 0; i < layers.size(); ++i) a.L[i] = layers[i];
+  a.img_floats = (int)image.size();
+  a.threshold = threshold;
+  a.idle_ticks = (uint64_t)(idle_seconds * 100e6);   // s_memrealtime runs at 100 MHz
+  in_lds_ = dense_serve_in_lds(a.L, a.nl);
+  ck(hipHostMalloc((void**)&stats_, 128, hipHostMallocMapped | hipHostMallocCoherent), "hipHostMalloc stats");
+  std::memset(stats_, 0, 128);
+  ck(hipHostGetDevicePointer((void**)&a.stats, stats_, 0), "device ptr stats");
+  ck(hipMalloc((void**)&img_d_, image.size() * sizeof(float)), "hipMalloc weight image");
+  ck(hipMemcpy(img_d_, image.data(), image.size() * sizeof(float), hipMemcpyHostToDevice), "copy weight image");
+  if (!scale.empty()) {
+    ck(hipMalloc((void**)&scale_d_, D * sizeof(float)), "hipMalloc scale");
+    ck(hipMalloc((void**)&shift_d_, D * sizeof(float)), "hipMalloc shift");
+    ck(hipMemcpy(scale_d_, scale.data(), D * sizeof(float), hipMemcpyHostToDevice), "copy scale");
+    ck(hipMemcpy(shift_d_, shift.data(), D * sizeof(float), hipMemcpyHostToDevice), "copy shift");
+  }
+  a.ctl = ctl_d_;
+  a.req = req_d_;
+  a.res = res_d_;
+  a.img = img_d_;
+  a.scale = scale_d_;
+  a.shift = shift_d_;
+  launch();
+}
+
+DenseServe::~DenseServe() {
+  try {
+    stop();
+  } catch (...) {
+  }
+  if (img_d_) (void)hipFree(img_d_);
+  if (scale_d_) (void)hipFree(scale_d_);
+  if (shift_d_) (void)hipFree(shift_d_);
+  if (stats_) (void)hipHostFree(stats_);
+}
+
+hipError_t DenseServe::launch_kernel() { return dense_serve_launch(args_, stream_); }
+
+uint64_t DenseServe::stats() const {
+  // the kernel stores the word after the pass's result words, which is what wait() polls: a
+  // call can return a moment before the word lands.  Bounded wait until it covers every event
+  // the host has gathered.
+  const uint32_t want = (uint32_t)complete_[0];
+  const auto t0 = std::chrono::steady_clock::now();
+  uint64_t v = load_acq(stats_);
+  while ((uint32_t)v != want && std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() < 0.5) {
+    cpu_relax();
+    v = load_acq(stats_);
+  }
+  return v;
+}
+
 int LSTMServe::checked_lanes(int device, int lanes, const std::vector<LstmServeLayer>& layers, int D, int T) {
   if (lanes == 1) return lanes;
   if (lanes < 1 || lanes > LSW_MAXLANES)

@@ -122,6 +122,38 @@ class AEServe : public ServeRing {
   float* shift_d_ = nullptr;
 };
 
+// Dense stacks of any depth (dense_serve.hip): 1..8 Dense layers up to 512 wide, rows of up to
+// 32 features, the last layer one unit per feature; one lane, up to DSV_EB events per pass.
+class DenseServe : public ServeRing {
+ public:
+  // image: the packed weight image (ops/serve.py dense_serve_image; sml_ops.h), layers: its table
+  DenseServe(int device, int nslots, const std::vector<float>& image, const std::vector<DenseServeLayer>& layers,
+             int D, const std::vector<float>& scale, const std::vector<float>& shift, float threshold,
+             double idle_seconds);
+  ~DenseServe() override;
+  // where the resident kernel keeps the image: "lds" | "stream"
+  const char* kernel() const { return in_lds_ ? "lds" : "stream"; }
+  // passes the kernel ran and events they served since construction (its stats word, read once
+  // it covers every event this host has gathered)
+  uint64_t passes() const { return stats() >> 32; }
+  uint64_t events() const { return stats() & 0xffffffffull; }
+
+ protected:
+  hipError_t launch_kernel() override;
+
+ private:
+  // every limit, before the base class allocates the rings; returns D
+  static int checked_D(const std::vector<float>& image, const std::vector<DenseServeLayer>& layers, int D,
+                       const std::vector<float>& scale, const std::vector<float>& shift);
+  uint64_t stats() const;
+  DenseServeArgs args_{};
+  bool in_lds_ = false;
+  uint64_t* stats_ = nullptr;   // host-mapped, 128 bytes
+  float* img_d_ = nullptr;
+  float* scale_d_ = nullptr;
+  float* shift_d_ = nullptr;
+};
+
 // LSTM forecaster (lstm_serve.hip): per car key, the last T events stay on the device; each
 // event is scored against the key's previous forecast and a new forecast is emitted.
 class LSTMServe : public ServeRing {

@@ -1477,6 +1477,31 @@ struct LSTMServePy : ServePy {
   int64_t nkeys() const override { return nk; }
 };
 
+// image: the packed weight image; layers: list of (in, out, act, w_off, b_off) tuples
+// (sml::DenseServeLayer).  Key-less: _io.ScoreLoop drives it through c_api() like AEServe.
+struct DenseServePy : ServePy {
+  DenseServePy(int device, int nslots, py::array_t<float, py::array::c_style | py::array::forcecast> image,
+               std::vector<std::vector<int>> layers, int D, py::object scale, py::object shift, double threshold,
+               double idle_seconds) {
+    std::vector<float> img(image.data(), image.data() + image.size());
+    std::vector<sml::DenseServeLayer> L;
+    for (const auto& t : layers) {
+      if (t.size() != 5) throw std::invalid_argument("layer descriptor: (in, out, act, w_off, b_off)");
+      L.push_back(sml::DenseServeLayer{t[0], t[1], t[2], t[3], t[4]});
+    }
+    std::vector<float> sc, sh;
+    if (!scale.is_none()) {
+      auto a = scale.cast<py::array_t<float, py::array::c_style | py::array::forcecast>>();
+      auto b = shift.cast<py::array_t<float, py::array::c_style | py::array::forcecast>>();
+      sc.assign(a.data(), a.data() + a.size());
+      sh.assign(b.data(), b.data() + b.size());
+    }
+    c10::hip::HIPGuard guard(device);
+    s = std::make_unique<sml::DenseServe>(device, nslots, img, L, D, sc, sh, (float)threshold, idle_seconds);
+  }
+  sml::DenseServe& dense() { return *static_cast<sml::DenseServe*>(s.get()); }
+};
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -1691,6 +1716,23 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
             return out;
           },
           "events each lane completed since construction or reset_keys (its completion counter)");
+  py::class_<DenseServePy, ServePy>(m, "DenseServe",
+                                    "persistent per-event scorer for Dense stacks of any depth, up to 512 wide")
+      .def(py::init<int, int, py::array_t<float, py::array::c_style | py::array::forcecast>,
+                    std::vector<std::vector<int>>, int, py::object, py::object, double, double>(),
+           py::arg("device"), py::arg("nslots"), py::arg("image"), py::arg("layers"), py::arg("D"),
+           py::arg("scale") = py::none(), py::arg("shift") = py::none(), py::arg("threshold") = 5.0,
+           py::arg("idle_seconds") = 2.0)
+      .def_property_readonly("kernel", [](DenseServePy& p) { return std::string(p.dense().kernel()); },
+                             "where the resident kernel keeps the weight image: lds | stream")
+      .def_property_readonly("passes", [](DenseServePy& p) { return p.dense().passes(); },
+                             "passes the kernel ran since construction")
+      .def_property_readonly("events", [](DenseServePy& p) { return p.dense().events(); },
+                             "events those passes served");
+  m.attr("DSV_MAXW") = (int)sml::DSV_MAXW;
+  m.attr("DSV_MAXLAYERS") = (int)sml::DSV_MAXLAYERS;
+  m.attr("DSV_EB") = (int)sml::DSV_EB;
+  m.attr("DSV_LDS_IMAGE_BYTES") = (int)sml::DSV_LDS_IMAGE_BYTES;
   m.def("lstm_head", &lstm_head, "fused LSTM Dense head: forward, MSE + accuracy, dW / db, dh (one pass + fold)",
         py::arg("h"), py::arg("W"), py::arg("b"), py::arg("y"), py::arg("gscale"), py::arg("grad"), py::arg("map"),
         py::arg("acc"), py::arg("out") = py::none(), py::arg("div0") = 1.0, py::arg("div1") = 1.0,
