@@ -46,6 +46,10 @@ def _flags(p):
                    help="under torchrun: each rank's share of the partitions (streamml.kafka.assign)")
     p.add_argument("--native-feed", action="store_true", help="ROCm: the C++ partition-parallel feed")
     p.add_argument("--feed-workers", type=int, default=4)
+    p.add_argument("--layers", default=None,
+                   help="hidden widths of a Dense stack, e.g. 64,16,64 (18 in, 18 out; tanh / relu alternate, relu "
+                        "last): trains an nn.Sequential instead of the 18-14-7-7-18 autoencoder and saves a Keras "
+                        ".h5 that `serve --model dense` accepts; with it, predict loads the file as such a stack")
     p.add_argument("--precision", default=None, choices=["fp32", "bf16"],
                    help="small-batch trainer contractions (Keras batch <= 128): fp32 (Keras-exact, default) or "
                         "bf16 MFMAs with fp32 master weights / Adam (compile(minibatch_precision=...))")
@@ -90,9 +94,53 @@ def _train(ns, servers, cfg, epochs, batch_size, out_path):
     return ae
 
 
+def _hidden_widths(spec: str):
+    widths = [int(w) for w in spec.split(",") if w.strip()]
+    if not widths or any(w < 1 for w in widths):
+        raise SystemExit(f"--layers wants positive hidden widths such as 64,16,64, not {spec!r}")
+    return widths
+
+
+def _train_layers(ns, servers, cfg, epochs, batch_size, out_path):
+    """``--layers``: an 18 -> hidden widths -> 18 Dense stack with the reference's tanh / relu
+    pattern, trained by ``nn.Model.fit`` on the normal events, normalised as ``normalize_fn`` does
+    (on a ROCm device the persistent Dense trainer takes stacks inside its limits)."""
+    from .. import nn
+    if _world() > 1:
+        raise SystemExit("--layers trains in one process: nn.Model.fit has no share of a torchrun job's partitions "
+                         "to give each rank (run it without torchrun)")
+    widths = _hidden_widths(ns.layers) + [18]
+    acts = ["tanh" if i % 2 == 0 else "relu" for i in range(len(widths))]
+    acts[-1] = "relu"
+    model = nn.Sequential([nn.Dense(u, activation=a, input_shape=(18,) if i == 0 else None)
+                           for i, (u, a) in enumerate(zip(widths, acts))], device=ns.device, seed=ns.seed)
+    model.compile(optimizer="adam", loss="mean_squared_error", metrics=["accuracy"])
+    model.summary()
+    training = _stream(ns, servers, cfg).filter_normal(device=True).normalize()
+    t0 = time.perf_counter()
+    model.fit(training, epochs=epochs, batch_size=batch_size, steps_per_epoch=ns.take, verbose=2)
+    print(f"Training complete ({time.perf_counter() - t0:.2f}s, engine {model.last_fit_engine})", flush=True)
+    model.save(out_path)
+    model.dist_rank = 0
+    return model
+
+
+def _load(ns, path):
+    """The saved model: the generic Dense stack under ``--layers`` (it reads normalised rows), else
+    the autoencoder with the normaliser fused into its kernels."""
+    if ns.layers:
+        from ..nn import load_model
+        return load_model(path, device=ns.device)
+    from ..models.autoencoder import load_model
+    return load_model(path, device=ns.device, input_normalizer="cardata")
+
+
 def _predict(ns, servers, cfg, model, batch_size, result_topic):
     from ..nn.callbacks import KafkaPredictionSink
-    data = _stream(ns, servers, cfg).batch(batch_size).skip(ns.skip).take(ns.predict_take)
+    events = _stream(ns, servers, cfg)
+    if ns.layers:
+        events = events.normalize()
+    data = events.batch(batch_size).skip(ns.skip).take(ns.predict_take)
     cbs = []
     if result_topic:
         sink = KafkaPredictionSink(batch_size, result_topic, servers, cfg, with_score=ns.with_score)
@@ -111,7 +159,6 @@ def main_v3(argv: Sequence[str]) -> int:
     if mode not in ("train", "predict"):
         print("Mode is invalid, must be either 'train' or 'predict':", mode)
         return 1
-    from ..models.autoencoder import load_model
     from ..utils.model_store import autoencoder_store
 
     servers = common.prepare_servers(ns.servers, ns.topic, seed=ns.synthetic_seed, schema=ns.schema)
@@ -120,7 +167,7 @@ def main_v3(argv: Sequence[str]) -> int:
     path = common.model_path(ns.workdir, ns.model_file)
     batch_size = ns.batch_size or 100
     if mode == "train":
-        ae = _train(ns, servers, cfg, ns.epochs or 20, batch_size, path)
+        ae = (_train_layers if ns.layers else _train)(ns, servers, cfg, ns.epochs or 20, batch_size, path)
         if ae.dist_rank == 0:
             url = store.upload(path, "/" + ns.model_file)
             print("Model stored successfully", ns.model_file, url, flush=True)
@@ -130,7 +177,7 @@ def main_v3(argv: Sequence[str]) -> int:
         print("Downloading model", ns.model_file, flush=True)
         store.download("/" + ns.model_file, path)
         print("Loading model", flush=True)
-        model = load_model(path, device=ns.device, input_normalizer="cardata")
+        model = _load(ns, path)
         _predict(ns, servers, cfg, model, batch_size, ns.result_topic)
     return 0
 
@@ -139,17 +186,15 @@ def main_v1(argv: Sequence[str]) -> int:
     common.print_options(argv)
     ns = common.parse(argv, V1_USAGE, ["servers", "topic", "offset", "result_topic"], n_optional=1,
                       add_flags=_flags)
-    from ..models.autoencoder import load_model
-
     servers = common.prepare_servers(ns.servers, ns.topic, seed=ns.synthetic_seed, schema=ns.schema)
     cfg = common.kafka_config(ns.servers, ns.kafka_config)
     path = common.model_path(ns.workdir, "path_to_my_model.h5")
     batch_size = ns.batch_size or 32
-    ae = _train(ns, servers, cfg, ns.epochs or 5, batch_size, path)
+    ae = (_train_layers if ns.layers else _train)(ns, servers, cfg, ns.epochs or 5, batch_size, path)
     from ..parallel.dp import shutdown
     shutdown()
     if ae.dist_rank == 0:   # predict runs once, on rank 0
-        model = load_model(path, device=ns.device, input_normalizer="cardata")   # "recreate purely from the file"
+        model = _load(ns, path)   # "recreate purely from the file"
         _predict(ns, servers, cfg, model, batch_size, ns.result_topic)
     return 0
 

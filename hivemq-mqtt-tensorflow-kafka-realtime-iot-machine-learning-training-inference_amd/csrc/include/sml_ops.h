@@ -389,6 +389,71 @@ const char* dense_serve_check(const DenseServeLayer* L, int nl, int D, int64_t i
 bool dense_serve_in_lds(const DenseServeLayer* L, int nl);
 hipError_t dense_serve_launch(const DenseServeArgs& args, hipStream_t stream);
 
+// ---- persistent small-batch trainer for Dense stacks of any depth (dense_minibatch.hip) ----
+// One workgroup runs nsteps sequential Keras steps (forward, MSE + activity penalties, categorical
+// accuracy, backward, gradients, Adam) of a stack described by a table.  fp32 throughout; the
+// weights stay in LDS and every thread keeps the gradient and Adam moments of up to DMB_TPT 4x4
+// tiles of the kernels (and, for the tiles of a kernel's first four rows, of four bias elements)
+// in registers.
+enum : int {
+  DMB_MAXLAYERS = 8,
+  DMB_MAXW = 128,             // units / inputs of a layer
+  DMB_MAXBATCH = 128,
+  DMB_NT = 512,               // threads of the workgroup
+  DMB_TPT = 2,                // 4x4 parameter tiles a thread can own
+  DMB_CHUNK = 32,             // rows of a batch in LDS at a time
+  DMB_MAXPARAMS = DMB_NT * DMB_TPT * 16,   // kernel elements with both widths rounded up to 4
+  DMB_LDS_BYTES = 160 * 1024
+};
+struct DenseMBLayer {
+  int in, units;
+  int act;             // ACT_* code
+  int has_bias;
+  float l1, l2;        // activity regulariser of the layer's output
+  int w_off, b_off;    // float offsets of the [in, units] kernel and the bias in flat / m / v
+};
+// where the kernel keeps a layer in LDS (float offsets), derived from the table alone
+struct DenseMBLayerPlan {
+  int ip, up;          // in / units rounded up to 4
+  int ws;              // floats between two rows of the kernel image (up, or up + 4: see the kernel)
+  int lw, lb;          // kernel image [ip][ws], bias [up]
+  int la, ld;          // the layer's output [DMB_CHUNK][up] and its gradient (the last layer's share one buffer)
+  int tile0;           // first 4x4 tile (= owning thread) of the layer
+};
+struct DenseMBPlan {
+  int dp;              // input width rounded up to 4
+  int la0;             // input rows [DMB_CHUNK][dp]
+  int lyt;             // target rows [DMB_CHUNK][op] (= la0 when y is null)
+  int lstat;           // per-row loss / correct / penalty, then the step's totals
+  int wimg0, wimg1;    // the weight image (zero-filled at launch)
+  int ntiles;
+  int lds_floats;
+  DenseMBLayerPlan L[DMB_MAXLAYERS];
+};
+struct DenseMBArgs {
+  float* flat;
+  float* m;
+  float* v;
+  int64_t* iter;
+  const float* x;
+  int64_t ldx;
+  const float* y;      // null: y = x
+  int64_t ldy;
+  const int32_t* order;
+  int64_t n, row0;
+  int batch, nsteps;
+  int nl, D;
+  DenseMBLayer L[DMB_MAXLAYERS];
+  DenseMBPlan P;
+  float lr, beta1, beta2, eps;
+  float* out;          // [nsteps, 2]
+};
+// empty if the kernel can train the stack (D inputs, nl layers, parameter offsets inside nflat
+// floats, this batch size, targets of their own or y = x), else the limit it exceeds
+const char* dense_mb_check(const DenseMBLayer* L, int nl, int D, int batch, int64_t nflat, bool own_targets);
+DenseMBPlan dense_mb_plan(const DenseMBLayer* L, int nl, int D, bool own_targets);
+hipError_t dense_mb_launch(DenseMBArgs args, hipStream_t stream);
+
 // ---- fused MSE + categorical accuracy (loss.hip) ----
 bool mse_acc_supported(int F);
 // acc != null needs part: 2 * mse_acc_blocks(rows, F) floats of scratch (the block partials,

@@ -1117,6 +1117,87 @@ at::Tensor lstm_ref_train(const at::Tensor& flat, const at::Tensor& m, const at:
   return out;
 }
 
+// Table rows of the persistent Dense trainer: (in, units, act, has_bias, l1, l2, w_off, b_off).
+static int dense_mb_table(const std::vector<std::vector<double>>& table, sml::DenseMBLayer* L) {
+  TORCH_CHECK(table.size() <= (size_t)sml::DMB_MAXLAYERS, table.size(), " Dense layers: the persistent trainer takes 1..",
+              (int)sml::DMB_MAXLAYERS, " (MAX_LAYERS)");
+  int nl = 0;
+  for (const auto& t : table) {
+    TORCH_CHECK(t.size() == 8, "layer descriptor: (in, units, act, has_bias, l1, l2, w_off, b_off)");
+    L[nl++] = sml::DenseMBLayer{(int)t[0], (int)t[1], (int)t[2], (int)t[3], (float)t[4], (float)t[5], (int)t[6],
+                                (int)t[7]};
+  }
+  return nl;
+}
+
+// Empty when dense_minibatch.hip can train the stack at this batch size, else the limit it exceeds.
+std::string dense_mb_check(const std::vector<std::vector<double>>& table, int64_t batch, int64_t nflat,
+                           bool own_targets) {
+  if (table.empty() || table.size() > (size_t)sml::DMB_MAXLAYERS)
+    return std::to_string(table.size()) + " Dense layers: the persistent trainer takes 1.." +
+           std::to_string((int)sml::DMB_MAXLAYERS) + " (MAX_LAYERS)";
+  sml::DenseMBLayer L[sml::DMB_MAXLAYERS] = {};
+  const int nl = dense_mb_table(table, L);
+  return sml::dense_mb_check(L, nl, L[0].in, (int)std::min<int64_t>(batch, 1 << 30), nflat < 0 ? INT64_MAX : nflat,
+                             own_targets);
+}
+
+// nsteps consecutive Keras steps of a Dense stack in one launch (dense_minibatch.hip); flat / m / v /
+// iter are updated in place; returns [nsteps, 2] = (mean loss incl. penalties, rows with matching argmax).
+at::Tensor dense_mb_train(const at::Tensor& flat, const at::Tensor& m, const at::Tensor& v, const at::Tensor& iter,
+                          const std::vector<std::vector<double>>& table, const at::Tensor& x,
+                          const c10::optional<at::Tensor>& y, const c10::optional<at::Tensor>& order, int64_t row0,
+                          int64_t batch, int64_t nsteps, double lr, double beta1, double beta2, double eps) {
+  check_dev(flat, "flat", at::kFloat);
+  check_dev(m, "m", at::kFloat);
+  check_dev(v, "v", at::kFloat);
+  check_dev(x, "x", at::kFloat);
+  TORCH_CHECK(iter.is_cuda() && iter.scalar_type() == at::kLong && iter.numel() == 1, "iter must be a device int64[1]");
+  TORCH_CHECK(flat.is_contiguous() && m.is_contiguous() && v.is_contiguous() && m.numel() == flat.numel() &&
+                  v.numel() == flat.numel(), "flat / m / v must be contiguous and of one size");
+  const std::string why = dense_mb_check(table, batch, flat.numel(), y.has_value());
+  TORCH_CHECK(why.empty(), "dense_mb_train: ", why);
+  sml::DenseMBArgs a{};
+  a.nl = dense_mb_table(table, a.L);
+  a.D = a.L[0].in;
+  const int O = a.L[a.nl - 1].units;
+  TORCH_CHECK(x.dim() == 2 && x.size(1) == a.D && (x.size(1) == 1 || x.stride(1) == 1), "x must be [n, ", a.D,
+              "] rows with contiguous features");
+  const int64_t n = x.size(0);
+  if (y.has_value()) {
+    check_dev(*y, "y", at::kFloat);
+    TORCH_CHECK(y->dim() == 2 && y->size(0) == n && y->size(1) == O && (y->size(1) == 1 || y->stride(1) == 1),
+                "y must be [n, ", O, "] rows with contiguous features");
+  }
+  if (order.has_value()) {
+    TORCH_CHECK(order->is_cuda() && order->scalar_type() == at::kInt && order->is_contiguous() && order->numel() == n,
+                "order must be a device int32 permutation of the n samples");
+  }
+  TORCH_CHECK(nsteps >= 1 && nsteps < (1 << 30) && row0 >= 0 && row0 < n, "bad nsteps / row0");
+  c10::hip::HIPGuard guard(x.device().index());
+  auto out = at::zeros({nsteps, 2}, flat.options());
+  a.flat = flat.data_ptr<float>();
+  a.m = m.data_ptr<float>();
+  a.v = v.data_ptr<float>();
+  a.iter = iter.data_ptr<int64_t>();
+  a.x = x.data_ptr<float>();
+  a.ldx = x.stride(0);
+  a.y = y.has_value() ? y->data_ptr<float>() : nullptr;
+  a.ldy = y.has_value() ? y->stride(0) : 0;
+  a.order = order.has_value() ? order->data_ptr<int32_t>() : nullptr;
+  a.n = n;
+  a.row0 = row0;
+  a.batch = (int)batch;
+  a.nsteps = (int)nsteps;
+  a.lr = (float)lr;
+  a.beta1 = (float)beta1;
+  a.beta2 = (float)beta2;
+  a.eps = (float)eps;
+  a.out = out.data_ptr<float>();
+  SML_CHECK_HIP(sml::dense_mb_launch(a, cur_stream(x)));
+  return out;
+}
+
 // Fused LSTM Dense head (lstm_head.hip): returns dh = dy . W^T as bf16 [n, 16]; dW / db into grad
 // through map (the dense_wgrad slab layout), this step's [sum sq err, #correct] into acc, out =
 // acc / div, counter + 1.
@@ -1662,6 +1743,20 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("act") = 1, py::arg("lr") = 1e-3, py::arg("beta1") = 0.9, py::arg("beta2") = 0.999,
         py::arg("eps") = 1e-7);
   m.def("lstm_ref_train_params", &sml::lstm_ref_train_params);
+  m.def("dense_mb_train", &dense_mb_train,
+        "persistent trainer: nsteps Keras Adam steps of a Dense stack (table rows: in, units, act, has_bias, l1, l2, "
+        "w_off, b_off) in one launch",
+        py::arg("flat"), py::arg("m"), py::arg("v"), py::arg("iter"), py::arg("table"), py::arg("x"),
+        py::arg("y") = py::none(), py::arg("order") = py::none(), py::arg("row0") = 0, py::arg("batch") = 32,
+        py::arg("nsteps") = 1, py::arg("lr") = 1e-3, py::arg("beta1") = 0.9, py::arg("beta2") = 0.999,
+        py::arg("eps") = 1e-7);
+  m.def("dense_mb_check", &dense_mb_check, "empty if dense_mb_train can run the table at this batch, else the reason",
+        py::arg("table"), py::arg("batch"), py::arg("nflat") = -1, py::arg("own_targets") = false);
+  m.attr("DMB_MAXLAYERS") = (int)sml::DMB_MAXLAYERS;
+  m.attr("DMB_MAXW") = (int)sml::DMB_MAXW;
+  m.attr("DMB_MAXBATCH") = (int)sml::DMB_MAXBATCH;
+  m.attr("DMB_MAXPARAMS") = (int)sml::DMB_MAXPARAMS;
+  m.attr("DMB_LDS_BYTES") = (int)sml::DMB_LDS_BYTES;
   m.def("mlp_fwd", &mlp_fwd, "dropout(act(x . W + b)) on fp32 MFMA (x float32 or uint8 scaled by 1/255)",
         py::arg("x"), py::arg("W"), py::arg("b") = py::none(), py::arg("relu") = false, py::arg("keep") = 1.0,
         py::arg("seed") = 0, py::arg("step") = 0);

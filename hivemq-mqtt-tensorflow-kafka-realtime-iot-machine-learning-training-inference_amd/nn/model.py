@@ -113,6 +113,8 @@ class Model:
         self.metrics: List[str] = []
         self.hp = dict(lr=1e-3, beta_1=0.9, beta_2=0.999, epsilon=1e-7)
         self._fused = None
+        self._fused_arg: Optional[bool] = None
+        self.last_fit_engine: Optional[str] = None
         self._acc = None
         self._pending_opt_state = None
 
@@ -188,6 +190,7 @@ class Model:
         self._acc = torch.zeros(3, device=self.device, dtype=torch.float64 if self.device.type == "cpu"
                                 else torch.float32)
         self._fused = None
+        self._fused_arg = fused
         if fused is None:
             fused = self.device.type == "cuda"
         if fused:
@@ -248,6 +251,15 @@ class Model:
             self.fp.set(self._fused.get_weights())
             it, m, v = self._fused.backend.get_optimizer_state()
             self.opt.load_state(it, m, v)
+
+    def _sync_to_fused(self) -> None:
+        """After a layer-loop fit (``engine="layers"``) of a model that also holds the fused
+        autoencoder: hand it the trained weights and Adam state, since predict / evaluate / save
+        and the next fused fit go through it."""
+        if self._fused is not None:
+            self._fused.set_weights(self.fp.get())
+            it, m, v = self.opt.state()
+            self._fused.backend.set_optimizer_state(it, m, v)
 
     # ------------------------------------------------------------------ forward / loss
     def _forward(self, x: torch.Tensor, training: bool, logits_only: bool = False) -> torch.Tensor:
@@ -385,12 +397,26 @@ class Model:
 
     def fit(self, x=None, y=None, batch_size: int = 32, epochs: int = 1, verbose: int = 1,
             callbacks: Optional[Sequence[Callback]] = None, validation_data=None, shuffle: bool = True,
-            steps_per_epoch: Optional[int] = None, seed: int = 0, initial_epoch: int = 0) -> History:
+            steps_per_epoch: Optional[int] = None, seed: int = 0, initial_epoch: int = 0,
+            engine: str = "auto") -> History:
+        """``engine``: ``"auto"`` picks the fastest trainer the model and input allow -- the fused
+        kernel for the recognised 4-layer autoencoder, else the persistent Dense trainer
+        (``ops.dense_persistent``: one launch per epoch) for Dense stacks inside its limits on a
+        ROCm device, else the layer-by-layer loop; ``"persistent"`` insists on the persistent
+        trainer (``ValueError`` with the reason if it cannot run); ``"layers"`` runs the layer
+        loop for this call, also on the recognised autoencoder (whose fused backend then receives
+        the trained state), as ``compile(fused=False)`` does for every call.  ``last_fit_engine`` records the choice."""
+        if engine not in ("auto", "persistent", "layers"):
+            raise ValueError(f"engine must be 'auto', 'persistent' or 'layers', not {engine!r}")
         if not self.compiled:
             self.compile()
-        if self._fused is not None:
+        if self._fused is not None and engine == "persistent":
+            raise ValueError("engine='persistent' cannot run: this model is the recognised 4-layer autoencoder, "
+                             "which trains on the fused kernel")
+        if self._fused is not None and engine == "auto":
             if y is not None and y is not x:
                 raise ValueError("autoencoder fit expects y == x")
+            self.last_fit_engine = "fused"
             hist = self._fused.fit(x, epochs=epochs, batch_size=batch_size, verbose=verbose, callbacks=callbacks,
                                    validation_data=validation_data, shuffle=shuffle,
                                    steps_per_epoch=steps_per_epoch, seed=seed, initial_epoch=initial_epoch)
@@ -401,6 +427,16 @@ class Model:
         world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
         rank = dist.get_rank() if world > 1 else 0
         allreduce = allreduce_sum_ if world > 1 else None
+        if engine != "layers":
+            why = self._persistent_reason(x, y, batch_size, world)
+            if not why and engine == "auto" and self._fused_arg is False:
+                why = "compile(fused=False) keeps the layer-by-layer engine"
+            if not why:
+                return self._fit_persistent(x, y, batch_size, epochs, verbose, callbacks, validation_data, shuffle,
+                                            steps_per_epoch, seed, initial_epoch)
+            if engine == "persistent":
+                raise ValueError(f"engine='persistent' cannot run: {why}")
+        self.last_fit_engine = "layers"
         hist = History()
         cbs = [hist] + list(callbacks or [])
         for cb in cbs:
@@ -432,6 +468,7 @@ class Model:
             if "accuracy" in self.metrics or "acc" in self.metrics:
                 logs["accuracy"] = float(m["accuracy"])
             if validation_data is not None:
+                self._sync_to_fused()       # evaluate goes through the fused backend where there is one
                 vx = validation_data[0]
                 vy = validation_data[1] if len(validation_data) > 1 else None
                 vl, va = self.evaluate(vx, vy, batch_size=max(batch_size, 1024))
@@ -441,6 +478,125 @@ class Model:
             logs["_seconds"] = time.perf_counter() - t0
             logs["_rows"] = float(m["rows"])
             if verbose and rank == 0:
+                shown = " - ".join(f"{k}: {v:.4f}" for k, v in logs.items() if not k.startswith("_"))
+                print(f"Epoch {epoch + 1}/{epochs}\n{steps} steps - {logs['_seconds']:.2f}s - {shown}", flush=True)
+            for cb in cbs:
+                cb.on_epoch_end(epoch, dict(logs))
+            if self.stop_training:
+                break
+        for cb in cbs:
+            cb.on_train_end()
+        self._sync_to_fused()
+        return hist
+
+    # ------------------------------------------------------------------ persistent Dense trainer
+    # rows of a Stream staged on the device per launch (rounded down to a multiple of the batch)
+    STREAM_SEGMENT_ROWS = 1 << 18
+
+    def _persistent_reason(self, x, y, batch_size, world) -> str:
+        """Empty if ``ops.dense_persistent`` can run this fit, else why not."""
+        from ..data.stream import Stream
+        from ..ops import dense_persistent as dpers
+        if self.device.type != "cuda":
+            return "it needs a ROCm device"
+        if world > 1:
+            return "torch.distributed training stays on the layer engine"
+        own_targets = y is not None and y is not x
+        if isinstance(x, Stream):
+            if own_targets:
+                return "a Stream carries no targets of its own"
+        elif not isinstance(x, (np.ndarray, torch.Tensor, list, tuple)):
+            return "the input must be arrays, tensors or a Stream"
+        ok, why = dpers.supports(self, batch_size, own_targets=own_targets)
+        if not ok:
+            return why
+        if not isinstance(x, Stream):
+            xs = x if isinstance(x, torch.Tensor) else np.asarray(x)
+            if xs.ndim != 2 or xs.shape[1] != int(self._input_shape()[0]) or len(xs) == 0:
+                return f"x of shape {tuple(xs.shape)} is not [n, {int(self._input_shape()[0])}] rows"
+            if own_targets:
+                ys = y if isinstance(y, torch.Tensor) else np.asarray(y)
+                if ys.ndim != 2 or ys.shape[1] != int(self.output_shape[-1]) or len(ys) != len(xs):
+                    return f"y of shape {tuple(ys.shape)} is not [{len(xs)}, {int(self.output_shape[-1])}] rows"
+        return ""
+
+    def _fit_persistent(self, x, y, batch_size, epochs, verbose, callbacks, validation_data, shuffle,
+                        steps_per_epoch, seed, initial_epoch) -> History:
+        """One ``dense_minibatch`` launch per epoch (per segment of a Stream); the kernel updates
+        ``fp.flat / m / v / iter`` in place, so save / predict / evaluate see the trained state."""
+        from ..data.stream import Stream
+        from ..ops import dense_persistent as dpers
+        from ..parallel.fault import maybe_inject_range
+        self.last_fit_engine = "persistent"
+        B = int(batch_size)
+        stream = isinstance(x, Stream)
+        if not stream:
+            xd = self._prep_x(x).float()
+            yd = None if (y is None or y is x) else self._prep_y(y).float()
+            n = int(xd.shape[0])
+        hist = History()
+        cbs = [hist] + list(callbacks or [])
+        for cb in cbs:
+            cb.set_model(self)
+            cb.on_train_begin()
+        gstep = int(getattr(self, "_global_step", 0))
+        self.stop_training = False
+        for epoch in range(initial_epoch, epochs):
+            rng = np.random.default_rng([seed, 0, epoch])     # the layer loop's permutation (rank 0)
+            t0 = time.perf_counter()
+            for cb in cbs:
+                cb.on_epoch_begin(epoch)
+            results, weights, rows = [], [], 0     # weights: rows of each step (a launch's last may be partial)
+            if stream:
+                cap = None if steps_per_epoch is None else int(steps_per_epoch)
+                seg = max(self.STREAM_SEGMENT_ROWS // B, 1) * B
+                if cap is not None:
+                    seg = min(seg, max(cap, 1) * B)
+                steps = 0
+                for c in x.batch(seg):
+                    if cap is not None and steps >= cap:
+                        break
+                    xs = self._prep_x(c.x).float()
+                    k = -(-int(xs.shape[0]) // B)
+                    if cap is not None:
+                        k = min(k, cap - steps)
+                    maybe_inject_range(gstep, gstep + k, 0)
+                    results.append(dpers.train_steps(self, xs, None, B, k, 0, None))
+                    used = min(int(xs.shape[0]), k * B)
+                    weights += [B] * (k - 1) + [used - B * (k - 1)]
+                    rows += used
+                    steps += k
+                    gstep += k
+            else:
+                steps = -(-n // B)
+                if steps_per_epoch is not None:
+                    steps = min(steps, int(steps_per_epoch))
+                order = None
+                if shuffle:
+                    order = torch.from_numpy(rng.permutation(n).astype(np.int32)).to(self.device)
+                if steps > 0:
+                    maybe_inject_range(gstep, gstep + steps, 0)
+                    results.append(dpers.train_steps(self, xd, yd, B, steps, 0, order))
+                rows = min(n, steps * B)
+                weights = [B] * (steps - 1) + [rows - B * (steps - 1)] if steps > 0 else []
+                gstep += steps
+            self._global_step = gstep
+            # per-step (mean loss, correct rows) -> the epoch's row-weighted mean, as the layer loop
+            r = torch.cat(results).double().cpu().numpy() if results else np.zeros((0, 2))
+            w = np.asarray(weights, np.float64)
+            logs = {"loss": float((r[:, 0] * w).sum() / max(rows, 1))}
+            if "accuracy" in self.metrics or "acc" in self.metrics:
+                logs["accuracy"] = float(r[:, 1].sum() / max(rows, 1))
+            if validation_data is not None:
+                vx = validation_data[0]
+                vy = validation_data[1] if len(validation_data) > 1 else None
+                vl, va = self.evaluate(vx, vy, batch_size=max(B, 1024))
+                logs["val_loss"] = vl
+                if "accuracy" in logs:
+                    logs["val_accuracy"] = va
+            logs["_seconds"] = time.perf_counter() - t0
+            logs["_rows"] = float(rows)
+            if verbose:
                 shown = " - ".join(f"{k}: {v:.4f}" for k, v in logs.items() if not k.startswith("_"))
                 print(f"Epoch {epoch + 1}/{epochs}\n{steps} steps - {logs['_seconds']:.2f}s - {shown}", flush=True)
             for cb in cbs:
