@@ -114,12 +114,13 @@ def _train_layers(ns, servers, cfg, epochs, batch_size, out_path):
     acts[-1] = "relu"
     model = nn.Sequential([nn.Dense(u, activation=a, input_shape=(18,) if i == 0 else None)
                            for i, (u, a) in enumerate(zip(widths, acts))], device=ns.device, seed=ns.seed)
-    model.compile(optimizer="adam", loss="mean_squared_error", metrics=["accuracy"])
+    model.compile(optimizer="adam", loss="mean_squared_error", metrics=["accuracy"], minibatch_precision=ns.precision)
     model.summary()
     training = _stream(ns, servers, cfg).filter_normal(device=True).normalize()
     t0 = time.perf_counter()
     model.fit(training, epochs=epochs, batch_size=batch_size, steps_per_epoch=ns.take, verbose=2)
-    print(f"Training complete ({time.perf_counter() - t0:.2f}s, engine {model.last_fit_engine})", flush=True)
+    prec = f", precision {model.last_fit_precision}" if model.last_fit_precision else ""
+    print(f"Training complete ({time.perf_counter() - t0:.2f}s, engine {model.last_fit_engine}{prec})", flush=True)
     model.save(out_path)
     model.dist_rank = 0
     return model

@@ -492,13 +492,18 @@ DenseMBPlan dense_mb_plan(const DenseMBLayer* L, int nl, int D, bool own_targets
   return P;
 }
 
-const char* dense_mb_check(const DenseMBLayer* L, int nl, int D, int batch, int64_t nflat, bool own_targets) {
+const char* dense_mb_check(const DenseMBLayer* L, int nl, int D, int batch, int64_t nflat, bool own_targets,
+                           int precision) {
   static thread_local std::string why;
   why.clear();
   auto fail = [&](std::string s) {
     why = std::move(s);
     return why.c_str();
   };
+  if (precision != DMB_FP32 && precision != DMB_BF16)
+    return fail("precision " + std::to_string(precision) + " is neither fp32 (0) nor bf16 (1)");
+  const bool bf16 = precision == DMB_BF16;
+  auto pad = [&](int n) { return bf16 ? (n + 15) / 16 * 16 : pad4(n); };
   if (nl < 1 || nl > DMB_MAXLAYERS)
     return fail(std::to_string(nl) + " Dense layers: the persistent trainer takes 1.." + std::to_string(DMB_MAXLAYERS) +
                 " (MAX_LAYERS)");
@@ -518,24 +523,28 @@ const char* dense_mb_check(const DenseMBLayer* L, int nl, int D, int batch, int6
     if (L[l].w_off < 0 || L[l].w_off + nw > nflat ||
         (L[l].has_bias && (L[l].b_off < 0 || (int64_t)L[l].b_off + L[l].units > nflat)))
       return fail("layer " + std::to_string(l) + ": parameter offsets outside the flat buffer");
-    padded += (int64_t)pad4(L[l].in) * pad4(L[l].units);
+    padded += (int64_t)pad(L[l].in) * pad(L[l].units);
     prev = L[l].units;
   }
-  if (padded > DMB_MAXPARAMS)
+  if (bf16 && padded > DMB_MAXPARAMS_BF16)
+    return fail(std::to_string(padded) + " kernel elements (widths rounded up to 16): the limit is " +
+                std::to_string(DMB_MAXPARAMS_BF16) + " (MAX_PARAMS_BF16)");
+  if (!bf16 && padded > DMB_MAXPARAMS)
     return fail(std::to_string(padded) + " kernel elements (widths rounded up to 4): the limit is " +
                 std::to_string(DMB_MAXPARAMS) + " (MAX_PARAMS)");
   if (!own_targets && prev != D) return fail("y = x needs as many output units as inputs");
-  const DenseMBPlan P = dense_mb_plan(L, nl, D, own_targets);
-  if ((int64_t)P.lds_floats * 4 + STATIC_LDS > DMB_LDS_BYTES)
-    return fail(std::to_string((int64_t)P.lds_floats * 4 + STATIC_LDS) + " bytes of LDS: the limit is " +
-                std::to_string(DMB_LDS_BYTES) + " (LDS_BYTES)");
+  const int64_t need = (bf16 ? (int64_t)dense_mb_plan_bf16(L, nl, D, own_targets).lds_bytes
+                             : (int64_t)dense_mb_plan(L, nl, D, own_targets).lds_floats * 4) + STATIC_LDS;
+  if (need > DMB_LDS_BYTES)
+    return fail(std::to_string(need) + " bytes of LDS: the limit is " + std::to_string(DMB_LDS_BYTES) + " (LDS_BYTES)");
   return "";
 }
 
 hipError_t dense_mb_launch(DenseMBArgs a, hipStream_t stream) {
   const bool own_targets = a.y != nullptr;
-  if (dense_mb_check(a.L, a.nl, a.D, a.batch, INT64_MAX, own_targets)[0] != 0) return hipErrorInvalidValue;
+  if (dense_mb_check(a.L, a.nl, a.D, a.batch, INT64_MAX, own_targets, a.precision)[0] != 0) return hipErrorInvalidValue;
   if (a.nsteps < 1 || a.row0 < 0 || a.row0 >= a.n) return hipErrorInvalidValue;
+  if (a.precision == DMB_BF16) return dense_mb_launch_bf16(a, stream);
   a.P = dense_mb_plan(a.L, a.nl, a.D, own_targets);
   const size_t lds = sizeof(float) * (size_t)a.P.lds_floats;
   if (lds > 65536) {

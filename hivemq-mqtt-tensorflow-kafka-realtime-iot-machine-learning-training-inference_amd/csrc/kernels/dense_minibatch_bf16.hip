@@ -1,0 +1,525 @@
+// Persistent small-batch trainer for Dense stacks of any depth with every contraction on
+// v_mfma_f32_16x16x32_bf16 (sibling of dense_minibatch.hip: same launch shape, table, chunks,
+// outputs and Adam; opt-in through DenseMBArgs::precision).
+//
+// ONE workgroup of DMB_NT threads (8 waves) runs nsteps sequential Keras steps in one launch.
+// Rounding points (bf = round to nearest even bf16; everything else fp32):
+//   forward   z_l = b_l + sum_k bf(h_{l-1}[r,k]) bf(W_l[k,j]),  h_l = act(z_l) in fp32, h_0 = x;
+//             the fp32 h_l feeds the loss, the penalties, the accuracy and the activation derivative
+//   backward  g_{l-1}[r,i] = sum_j bf(dz_l[r,j]) bf(W_l[i,j]),  dz_{l-1} = act'(h_{l-1}) (g_{l-1} + penalty) in fp32
+//   weights   dW_l[i,j] = sum_r bf(h_{l-1}[r,i]) bf(dz_l[r,j]): K is the chunk's 32 rows, one MFMA per
+//             16x16 tile per chunk, accumulated in fp32 over the chunks of a step
+//   bias      db_l[j] = the fp32 column sum of the UNROUNDED dz_l, rows ascending (db_bf16 = False in
+//             the test oracle)
+//   Adam      sml_adam.h on fp32 masters; bf(W) is re-derived from the master after every update
+//
+// Memory plan (DenseMBPlanBF16, a pure function of the layer table; widths zero-padded to 16):
+//   * wave w owns the 16x16 kernel tiles w, w + 8, ... (8 at most) in the MFMA C layout (lane (c, g):
+//     kernel rows i0 + 4g .. + 3, column j0 + c) and keeps their fp32 master, gradient and both Adam
+//     moments in registers from launch to exit: 128 VGPRs of state.
+//   * LDS holds ONE bf16 weight image per layer, unit-major [up][ip + 8]: the forward pass reads its
+//     rows (ds_read_b128), the backward pass reads it transposed (ds_read_b64_tr_b16).
+//   * per 32-row chunk LDS holds the fp32 output of every layer (overwritten in place by its fp32
+//     pre-activation gradient once that is known), a bf16 image of every layer input and a bf16
+//     image of every pre-activation gradient, all [row][unit]: read by rows as the forward /
+//     backward operand and transposed as the two weight-gradient operands.
+//   * biases, their moments and gradients are fp32 in LDS, one thread per element.
+//   * row strides carry 16 bytes of padding, so 16 rows' 16-byte pieces fall on different banks.
+//   * the products are computed transposed (units or inputs on the C rows, batch rows on the lanes),
+//     so a lane ends with four consecutive units of one row: one 16-byte and one 8-byte LDS store.
+//   * padded units are forced to 0 on the way forward and padded units / rows to 0 gradient on the
+//     way back, so padded parameters see exactly 0 gradient, stay 0 and are never written back
+//     (sigmoid(0) = 0.5 cannot leak).  Every chunk computes all 32 rows: absent rows are zero inputs.
+// Every transposed read is executed by all 64 lanes of every wave (wave-uniform control flow; out-of-
+// range K pieces read a clamped address and are replaced by zeros).  The kernel synchronises with
+// __syncthreads() only and every loop bound is known at launch.
+#include "sml_common.h"
+#include "sml_ops.h"
+
+#include "sml_adam.h"
+
+namespace sml {
+namespace {
+
+constexpr int NT = DMB_NT, CH = DMB_CHUNK, NW = NT / 64, SLOTS = DMB_TILES_BF16 / NW;
+constexpr int STAT_SQ = 0, STAT_OK = CH, STAT_PEN = 2 * CH, STAT_TOT = 3 * CH;   // floats from lstat
+static_assert(CH == 32 && NW * SLOTS == DMB_TILES_BF16, "one MFMA K step per chunk; whole tiles per wave");
+
+typedef unsigned char lds_t;
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+
+__device__ __forceinline__ float* fptr(lds_t* S, int off) { return reinterpret_cast<float*>(S + off); }
+__device__ __forceinline__ f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
+__device__ __forceinline__ void st4(float* p, f32x4 v) { *reinterpret_cast<f32x4*>(p) = v; }
+__device__ __forceinline__ unsigned short to_bf16(float v) { return (unsigned short)(pack2(v, 0.0f) & 0xffffu); }
+
+__device__ __forceinline__ f32x4 mma(s16x8 a, s16x8 b, f32x4 c) {
+  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
+}
+
+// d(l1 * |h| + l2 * h^2) / dh, divided by the step's rows as Keras does
+__device__ __forceinline__ float pen_grad(float l1, float l2, float h, float inv_rows) {
+  const float sg = h > 0.0f ? 1.0f : h < 0.0f ? -1.0f : 0.0f;
+  return (l1 * sg + 2.0f * l2 * h) * inv_rows;
+}
+
+// MFMA operand read by rows: lane (c, g) gets elements k0 + 8g .. + 7 of row row0 + c of a bf16
+// image with `stride` bytes between rows; zeros where k0 + 8g >= kmax
+__device__ __forceinline__ s16x8 row8(const lds_t* S, int base, int stride, int row0, int k0, int kmax, int c, int g) {
+  const int k = k0 + 8 * g;
+  const bool in = k < kmax;
+  const s16x8 v = *reinterpret_cast<const s16x8*>(S + base + (row0 + c) * stride + 2 * (in ? k : 0));
+  const s16x8 z = {0, 0, 0, 0, 0, 0, 0, 0};
+  return in ? v : z;
+}
+
+// MFMA operand read transposed: lane (c, g) gets column col0 + c of the image's rows k0 + 8g .. + 7
+// (two ds_read_b64_tr_b16: lane 4q + p of a 16-lane group addresses row q, columns 4p .. 4p + 3 of a
+// 4 x 16 block); zeros where k0 + 8g >= kmax.  All 64 lanes must execute it.
+__device__ __forceinline__ s16x8 tr8(lds_t* S, int base, int stride, int k0, int kmax, int col0, int c, int g) {
+  const int k = k0 + 8 * g;
+  const bool in = k < kmax;
+  lds_t* p = S + base + ((in ? k : 0) + (c >> 2)) * stride + 2 * (col0 + 4 * (c & 3));
+  const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_bf16x4*)p);
+  const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_bf16x4*)(p + 4 * stride));
+  const s16x8 v = cat8(lo, hi);
+  const s16x8 z = {0, 0, 0, 0, 0, 0, 0, 0};
+  return in ? v : z;
+}
+
+// layer output, transposed product: C[unit j0 + 4g + e][row 16 rb + c] = b + sum_i W^T[j][i] h^T[i][r]
+__device__ __forceinline__ void fwd_layer(lds_t* S, const DenseMBLayer& L, const DenseMBLayerPlanBF16& P, int lprev,
+                                          int sprev, bool last, int wave, int c, int g) {
+  const int ntile = (P.up >> 4) * 2;
+  for (int t = wave; t < ntile; t += NW) {
+    const int j0 = (t >> 1) << 4, r0 = (t & 1) << 4;
+    f32x4 acc = ld4(fptr(S, P.lb) + j0 + 4 * g);
+    for (int k0 = 0; k0 < P.ip; k0 += 32) {
+      const s16x8 wa = row8(S, P.lw, 2 * P.ws, j0, k0, P.ip, c, g);
+      const s16x8 hb = row8(S, lprev, 2 * sprev, r0, k0, P.ip, c, g);
+      acc = mma(wa, hb, acc);
+    }
+    f32x4 h;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) h[e] = j0 + 4 * g + e < L.units ? act_fwd(L.act, acc[e]) : 0.0f;
+    st4(fptr(S, P.la) + (r0 + c) * P.hs + j0 + 4 * g, h);
+    if (!last) *reinterpret_cast<bf16x4*>(S + P.lhb + 2 * ((r0 + c) * P.bs + j0 + 4 * g)) = pack4(h);
+  }
+}
+
+// gradient of layer l - 1's output from layer l's, transposed product:
+// C[input i0 + 4g + e][row 16 rb + c] = sum_j W[i][j] dz^T[j][r]; then dz_{l-1} replaces h_{l-1}
+__device__ __forceinline__ void bwd_layer(lds_t* S, const DenseMBLayerPlanBF16& P, const DenseMBLayer& Lp,
+                                          const DenseMBLayerPlanBF16& Pp, int rows, float inv_rows, int wave, int c, int g) {
+  const int ntile = (P.ip >> 4) * 2;
+  const bool pen = Lp.l1 != 0.0f || Lp.l2 != 0.0f;
+  for (int t = wave; t < ntile; t += NW) {
+    const int i0 = (t >> 1) << 4, r0 = (t & 1) << 4;
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    for (int k0 = 0; k0 < P.up; k0 += 32) {
+      const s16x8 wa = tr8(S, P.lw, 2 * P.ws, k0, P.up, i0, c, g);
+      const s16x8 db = row8(S, P.ld, 2 * P.bs, r0, k0, P.up, c, g);
+      acc = mma(wa, db, acc);
+    }
+    float* hp = fptr(S, Pp.la) + (r0 + c) * Pp.hs + i0 + 4 * g;
+    const f32x4 h = ld4(hp);
+    f32x4 d;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      float gg = acc[e];
+      if (pen) gg += pen_grad(Lp.l1, Lp.l2, h[e], inv_rows);
+      gg = act_grad(Lp.act, h[e], gg);
+      d[e] = (i0 + 4 * g + e < Lp.units && r0 + c < rows) ? gg : 0.0f;
+    }
+    st4(hp, d);
+    *reinterpret_cast<bf16x4*>(S + Pp.ld + 2 * ((r0 + c) * Pp.bs + i0 + 4 * g)) = pack4(d);
+  }
+}
+
+// rows of one chunk on their way from global memory to LDS: row tid / LPR, columns tid % LPR + LPR e
+constexpr int LPR = NT / CH;            // lanes per row in the staging and loss phases
+constexpr int SE = DMB_MAXW / LPR;      // elements per lane of a row
+static_assert(LPR * CH == NT && LPR <= 32 && (LPR & (LPR - 1)) == 0 && SE * LPR == DMB_MAXW, "row phases: lanes per row");
+struct Stage {
+  float x[SE], y[SE];
+};
+
+__device__ __forceinline__ void stage_load(const DenseMBArgs& a, int O, int s, int k, int steps, Stage& st) {
+  const int r = threadIdx.x / LPR, q = threadIdx.x % LPR;
+  int rows = 0;
+  int64_t pos = 0;
+  if (s < steps) {
+    const int64_t base = a.row0 + (int64_t)s * a.batch;
+    const int64_t left = a.n - base;
+    const int rows_s = left < a.batch ? (int)left : a.batch;
+    rows = rows_s - k * CH < CH ? rows_s - k * CH : CH;
+    pos = base + k * CH + r;
+  }
+  const bool rv = r < rows;
+  int64_t src = 0;
+  if (rv) {
+    src = a.order ? (int64_t)a.order[pos] : pos;
+    src = src < 0 ? 0 : src >= a.n ? a.n - 1 : src;
+  }
+#pragma unroll
+  for (int e = 0; e < SE; ++e) {
+    const int c = q + LPR * e;
+    st.x[e] = (rv && c < a.D) ? a.x[src * a.ldx + c] : 0.0f;
+    st.y[e] = (a.y != nullptr && rv && c < O) ? a.y[src * a.ldy + c] : 0.0f;
+  }
+}
+
+__device__ __forceinline__ void stage_store(lds_t* S, const DenseMBArgs& a, const DenseMBPlanBF16& P, int op, const Stage& st) {
+  const int r = threadIdx.x / LPR, q = threadIdx.x % LPR;
+  float* xr = fptr(S, P.la0) + r * P.xs;
+  unsigned short* xb = reinterpret_cast<unsigned short*>(S + P.lxb) + r * P.xbs;
+  float* yr = fptr(S, P.lyt) + r * P.ys;
+#pragma unroll
+  for (int e = 0; e < SE; ++e) {
+    const int c = q + LPR * e;
+    if (c < P.dp) {
+      xr[c] = st.x[e];
+      xb[c] = to_bf16(st.x[e]);
+    }
+    if (a.y != nullptr && c < op) yr[c] = st.y[e];
+  }
+}
+
+// per row (LPR lanes each): squared error, categorical accuracy (ties -> lowest index), activity
+// penalties; the last layer's output is replaced by its pre-activation gradient (fp32 and bf16)
+__device__ __forceinline__ void loss_phase(lds_t* S, const DenseMBLayer* sL, const DenseMBLayerPlanBF16* sP, int nl, int lyt,
+                                           int ys, int lstat, int rows, float inv_n, float inv_rows) {
+  const int r = threadIdx.x / LPR, q = threadIdx.x % LPR;
+  const bool rv = r < rows;
+  float pen = 0.0f;
+  for (int l = 0; l < nl; ++l) {
+    const float l1 = sL[l].l1, l2 = sL[l].l2;
+    if (l1 == 0.0f && l2 == 0.0f) continue;
+    float s1 = 0.0f, s2 = 0.0f;
+    const float* hr = fptr(S, sP[l].la) + r * sP[l].hs;
+    for (int j = q; j < sL[l].units; j += LPR) {
+      const float h = hr[j];
+      s1 += fabsf(h);
+      s2 = fmaf(h, h, s2);
+    }
+    pen += l1 * s1 + l2 * s2;
+  }
+  const DenseMBLayer& L = sL[nl - 1];
+  const DenseMBLayerPlanBF16& P = sP[nl - 1];
+  const bool lpen = L.l1 != 0.0f || L.l2 != 0.0f;
+  float* yrow = fptr(S, P.la) + r * P.hs;
+  unsigned short* drow = reinterpret_cast<unsigned short*>(S + P.ld) + r * P.bs;
+  const float* trow = fptr(S, lyt) + r * ys;
+  float sq = 0.0f, by = -INFINITY, bt = -INFINITY;
+  int iy = 1 << 30, it = 1 << 30;
+  for (int j = q; j < P.up; j += LPR) {
+    const bool valid = rv && j < L.units;
+    const float yv = yrow[j], tv = j < L.units ? trow[j] : 0.0f;
+    const float e = yv - tv;
+    if (valid) {
+      sq = fmaf(e, e, sq);
+      if (yv > by) { by = yv; iy = j; }
+      if (tv > bt) { bt = tv; it = j; }
+    }
+    float g = 2.0f * e * inv_n;
+    if (lpen) g += pen_grad(L.l1, L.l2, yv, inv_rows);
+    const float d = valid ? act_grad(L.act, yv, g) : 0.0f;
+    yrow[j] = d;
+    drow[j] = to_bf16(d);
+  }
+#pragma unroll
+  for (int o = LPR / 2; o > 0; o >>= 1) {
+    sq += __shfl_xor(sq, o, 64);
+    pen += __shfl_xor(pen, o, 64);
+    const float oy = __shfl_xor(by, o, 64), ot = __shfl_xor(bt, o, 64);
+    const int oiy = __shfl_xor(iy, o, 64), oit = __shfl_xor(it, o, 64);
+    if (oy > by || (oy == by && oiy < iy)) { by = oy; iy = oiy; }
+    if (ot > bt || (ot == bt && oit < it)) { bt = ot; it = oit; }
+  }
+  if (q == 0) {
+    float* st = fptr(S, lstat);
+    st[STAT_SQ + r] = rv ? sq : 0.0f;
+    st[STAT_OK + r] = (rv && iy == it) ? 1.0f : 0.0f;
+    st[STAT_PEN + r] = rv ? pen : 0.0f;
+  }
+}
+
+// the 16x16 tile of a slot of this wave from its table entry (wave-uniform, read once at launch, so
+// it lives in SGPRs): false if the slot is empty (entry -1)
+struct TilePos {
+  int l, i0, j0;
+};
+__device__ __forceinline__ bool tile_of(int info, TilePos& t) {
+  if (info < 0) return false;
+  t.l = info >> 16;
+  t.i0 = ((info >> 8) & 0xff) << 4;
+  t.j0 = (info & 0xff) << 4;
+  return true;
+}
+
+__global__ __launch_bounds__(NT) void dense_mb_bf16_kernel(const DenseMBArgs a, const DenseMBPlanBF16 P) {
+  extern __shared__ __attribute__((aligned(16))) lds_t S[];
+  __shared__ DenseMBLayer sL[DMB_MAXLAYERS];
+  __shared__ DenseMBLayerPlanBF16 sP[DMB_MAXLAYERS];
+  const int tid = threadIdx.x, nl = a.nl;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63, c = lane & 15, g = lane >> 4;
+  if (tid == 0) {
+#pragma unroll
+    for (int l = 0; l < DMB_MAXLAYERS; ++l) {
+      sL[l] = a.L[l];
+      sP[l] = P.L[l];
+    }
+  }
+  if (tid < P.ntiles) {   // tile table: layer, input block, unit block (unit blocks fastest)
+    int l = 0;
+    for (int k = 1; k < nl; ++k)
+      if (tid >= P.L[k].tile0) l = k;
+    const int k = tid - P.L[l].tile0, nj = P.L[l].up >> 4;
+    reinterpret_cast<int*>(S + P.ltile)[tid] = (l << 16) | ((k / nj) << 8) | (k % nj);
+  }
+  if (tid < 3) fptr(S, P.lstat)[STAT_TOT + tid] = 0.0f;
+  __syncthreads();
+
+  // ---- the tiles this wave owns: fp32 masters and moments into registers, bf16 image into LDS ----
+  f32x4 Tw[SLOTS], Tg[SLOTS], Tm[SLOTS], Tv[SLOTS];
+  int ti[SLOTS];
+#pragma unroll
+  for (int u = 0; u < SLOTS; ++u) {
+    const int id = wave + NW * u;
+    ti[u] = id < P.ntiles ? __builtin_amdgcn_readfirstlane(reinterpret_cast<const int*>(S + P.ltile)[id]) : -1;
+  }
+#pragma unroll
+  for (int u = 0; u < SLOTS; ++u) {
+    Tw[u] = Tg[u] = Tm[u] = Tv[u] = f32x4{0.f, 0.f, 0.f, 0.f};
+    TilePos t;
+    if (!tile_of(ti[u], t)) continue;
+    const DenseMBLayer& L = sL[t.l];
+    const int j = t.j0 + c;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const int i = t.i0 + 4 * g + e;
+      if (i < L.in && j < L.units) {
+        const unsigned f = (unsigned)(L.w_off + i * L.units + j);
+        Tw[u][e] = a.flat[f];
+        Tm[u][e] = a.m[f];
+        Tv[u][e] = a.v[f];
+      }
+    }
+    *reinterpret_cast<bf16x4*>(S + sP[t.l].lw + 2 * (j * sP[t.l].ws + t.i0 + 4 * g)) = pack4(Tw[u]);
+  }
+  // biases: thread (layer tid / 128 + 4k, unit tid % 128); state b, m, v, gradient = 4 x [up] fp32
+  for (int l = tid >> 7; l < nl; l += NT / DMB_MAXW) {
+    const int j = tid & (DMB_MAXW - 1), up = sP[l].up;
+    if (j >= up) continue;
+    const bool real = sL[l].has_bias && j < sL[l].units;
+    const unsigned f = (unsigned)(sL[l].b_off + j);
+    float* bs = fptr(S, sP[l].lb);
+    bs[j] = real ? a.flat[f] : 0.0f;
+    bs[up + j] = real ? a.m[f] : 0.0f;
+    bs[2 * up + j] = real ? a.v[f] : 0.0f;
+    bs[3 * up + j] = 0.0f;
+  }
+
+  const int64_t it0 = *a.iter;
+  const int O = sL[nl - 1].units, op = sP[nl - 1].up;
+  const int64_t avail = a.n - a.row0;
+  const int64_t maxsteps = avail > 0 ? (avail + a.batch - 1) / a.batch : 0;
+  const int steps = (int)(maxsteps < a.nsteps ? maxsteps : a.nsteps);
+
+  Stage st;
+  stage_load(a, O, 0, 0, steps, st);
+  for (int s = 0; s < steps; ++s) {
+    const int64_t left = avail - (int64_t)s * a.batch;
+    const int rows_s = left < a.batch ? (int)left : a.batch;
+    const int chunks = (rows_s + CH - 1) / CH;
+    const float inv_rows = 1.0f / (float)rows_s, inv_n = 1.0f / ((float)rows_s * (float)O);
+    for (int k = 0; k < chunks; ++k) {
+      const int rows = rows_s - k * CH < CH ? rows_s - k * CH : CH;
+      stage_store(S, a, P, op, st);
+      if (k + 1 < chunks) stage_load(a, O, s, k + 1, steps, st);
+      else stage_load(a, O, s + 1, 0, steps, st);
+      __syncthreads();
+      // ---- forward ----
+      for (int l = 0; l < nl; ++l) {
+        fwd_layer(S, a.L[l], P.L[l], l == 0 ? P.lxb : P.L[l - 1].lhb, l == 0 ? P.xbs : P.L[l - 1].bs, l == nl - 1, wave, c, g);
+        __syncthreads();
+      }
+      loss_phase(S, sL, sP, nl, P.lyt, P.ys, P.lstat, rows, inv_n, inv_rows);
+      __syncthreads();
+      // ---- backward ----
+      for (int l = nl - 1; l >= 1; --l) {
+        bwd_layer(S, P.L[l], a.L[l - 1], P.L[l - 1], rows, inv_rows, wave, c, g);
+        __syncthreads();
+      }
+      // ---- weight gradients into the owners' registers: dW[i][j] += sum_r h^T[i][r] dz[r][j] ----
+#pragma unroll
+      for (int u = 0; u < SLOTS; ++u) {
+        TilePos t;
+        if (!tile_of(ti[u], t)) continue;
+        const int lp = t.l > 0 ? t.l - 1 : 0;
+        const int lh = t.l == 0 ? P.lxb : P.L[lp].lhb, sh = t.l == 0 ? P.xbs : P.L[lp].bs;
+        const s16x8 ha = tr8(S, lh, 2 * sh, 0, CH, t.i0, c, g);
+        const s16x8 db = tr8(S, P.L[t.l].ld, 2 * P.L[t.l].bs, 0, CH, t.j0, c, g);
+        Tg[u] = mma(ha, db, Tg[u]);
+      }
+      // ---- bias gradients: fp32 column sums of the unrounded dz, rows ascending ----
+      for (int l = tid >> 7; l < nl; l += NT / DMB_MAXW) {
+        const int j = tid & (DMB_MAXW - 1), up = sP[l].up;
+        if (j >= up || !sL[l].has_bias) continue;
+        const float* dp = fptr(S, sP[l].la) + j;
+        float* gb = fptr(S, sP[l].lb) + 3 * up + j;
+        float sum = *gb;
+        for (int r = 0; r < CH; ++r) sum += dp[r * sP[l].hs];
+        *gb = sum;
+      }
+      if (tid < 3) {   // the step's squared error / correct rows / penalty, rows ascending
+        float* stt = fptr(S, P.lstat);
+        float tot = stt[STAT_TOT + tid];
+        for (int r = 0; r < rows; ++r) tot += stt[CH * tid + r];
+        stt[STAT_TOT + tid] = tot;
+      }
+      __syncthreads();
+    }
+    // ---- Adam on the owned masters; the bf16 image is re-derived from them ----
+    const float lr_t = adam_lr_t(a.lr, a.beta1, a.beta2, (float)(it0 + s + 1));
+#pragma unroll
+    for (int u = 0; u < SLOTS; ++u) {
+      TilePos t;
+      if (!tile_of(ti[u], t)) continue;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        float mm, vv, pn;
+        adam_update(Tg[u][e], Tm[u][e], Tv[u][e], Tw[u][e], lr_t, a.beta1, a.beta2, a.eps, 1.0f, mm, vv, pn);
+        Tm[u][e] = mm;
+        Tv[u][e] = vv;
+        Tw[u][e] = pn;
+      }
+      Tg[u] = f32x4{0.f, 0.f, 0.f, 0.f};
+      *reinterpret_cast<bf16x4*>(S + P.L[t.l].lw + 2 * ((t.j0 + c) * P.L[t.l].ws + t.i0 + 4 * g)) = pack4(Tw[u]);
+    }
+    for (int l = tid >> 7; l < nl; l += NT / DMB_MAXW) {
+      const int j = tid & (DMB_MAXW - 1), up = sP[l].up;
+      if (j >= up) continue;
+      float* bs = fptr(S, sP[l].lb);
+      float mm, vv, pn;
+      adam_update(bs[3 * up + j], bs[up + j], bs[2 * up + j], bs[j], lr_t, a.beta1, a.beta2, a.eps, 1.0f, mm, vv, pn);
+      bs[j] = pn;
+      bs[up + j] = mm;
+      bs[2 * up + j] = vv;
+      bs[3 * up + j] = 0.0f;
+    }
+    if (tid == 0) {
+      const float* tot = fptr(S, P.lstat) + STAT_TOT;
+      a.out[2 * s] = tot[0] * inv_n + tot[2] * inv_rows;
+      a.out[2 * s + 1] = tot[1];
+    }
+    __syncthreads();
+    if (tid < 3) fptr(S, P.lstat)[STAT_TOT + tid] = 0.0f;   // next touched after the next chunk's barriers
+  }
+
+  // ---- write the real parameters and their moments back ----
+#pragma unroll
+  for (int u = 0; u < SLOTS; ++u) {
+    TilePos t;
+    if (!tile_of(ti[u], t)) continue;
+    const DenseMBLayer& L = sL[t.l];
+    const int j = t.j0 + c;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const int i = t.i0 + 4 * g + e;
+      if (i < L.in && j < L.units) {
+        const unsigned f = (unsigned)(L.w_off + i * L.units + j);
+        a.flat[f] = Tw[u][e];
+        a.m[f] = Tm[u][e];
+        a.v[f] = Tv[u][e];
+      }
+    }
+  }
+  for (int l = tid >> 7; l < nl; l += NT / DMB_MAXW) {
+    const int j = tid & (DMB_MAXW - 1), up = sP[l].up;
+    if (!sL[l].has_bias || j >= sL[l].units) continue;
+    const unsigned f = (unsigned)(sL[l].b_off + j);
+    const float* bs = fptr(S, sP[l].lb);
+    a.flat[f] = bs[j];
+    a.m[f] = bs[up + j];
+    a.v[f] = bs[2 * up + j];
+  }
+  if (tid == 0) *a.iter = it0 + steps;
+}
+
+constexpr int pad16(int n) { return (n + 15) / 16 * 16; }
+
+}  // namespace
+
+DenseMBPlanBF16 dense_mb_plan_bf16(const DenseMBLayer* L, int nl, int D, bool own_targets) {
+  DenseMBPlanBF16 P{};
+  int off = 0, tiles = 0;
+  P.dp = pad16(D);
+  P.xs = P.dp + 4;
+  P.la0 = off;
+  off += CH * P.xs * 4;
+  P.xbs = P.dp + 8;
+  P.lxb = off;
+  off += CH * P.xbs * 2;
+  int prev = P.dp;
+  for (int l = 0; l < nl; ++l) {
+    DenseMBLayerPlanBF16& q = P.L[l];
+    q.ip = prev;
+    q.up = pad16(L[l].units);
+    q.ws = q.ip + 8;
+    q.lw = off;
+    off += q.up * q.ws * 2;
+    q.lb = off;
+    off += 4 * q.up * 4;
+    q.tile0 = tiles;
+    tiles += (q.ip >> 4) * (q.up >> 4);
+    prev = q.up;
+  }
+  for (int l = 0; l < nl; ++l) {
+    P.L[l].hs = P.L[l].up + 4;
+    P.L[l].la = off;
+    off += CH * P.L[l].hs * 4;
+  }
+  for (int l = 0; l < nl; ++l) {
+    P.L[l].bs = P.L[l].up + 8;
+    P.L[l].lhb = 0;
+    if (l < nl - 1) {
+      P.L[l].lhb = off;
+      off += CH * P.L[l].bs * 2;
+    }
+  }
+  for (int l = 0; l < nl; ++l) {
+    P.L[l].ld = off;
+    off += CH * P.L[l].bs * 2;
+  }
+  if (own_targets) {
+    P.ys = prev + 4;
+    P.lyt = off;
+    off += CH * P.ys * 4;
+  } else {
+    P.ys = P.xs;
+    P.lyt = P.la0;
+  }
+  P.lstat = off;
+  off += 4 * CH * 4;
+  P.ltile = off;
+  off += DMB_TILES_BF16 * 4;
+  P.ntiles = tiles;
+  P.lds_bytes = off;
+  return P;
+}
+
+hipError_t dense_mb_launch_bf16(const DenseMBArgs& a, hipStream_t stream) {
+  const DenseMBPlanBF16 P = dense_mb_plan_bf16(a.L, a.nl, a.D, a.y != nullptr);
+  if (P.ntiles > DMB_TILES_BF16) return hipErrorInvalidValue;
+  const size_t lds = (size_t)P.lds_bytes;
+  if (lds > 65536) {
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(dense_mb_bf16_kernel),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL(dense_mb_bf16_kernel, dim3(1), dim3(NT), lds, stream, a, P);
+  return hipGetLastError();
+}
+
+}  // namespace sml

@@ -1132,14 +1132,14 @@ static int dense_mb_table(const std::vector<std::vector<double>>& table, sml::De
 
 // Empty when dense_minibatch.hip can train the stack at this batch size, else the limit it exceeds.
 std::string dense_mb_check(const std::vector<std::vector<double>>& table, int64_t batch, int64_t nflat,
-                           bool own_targets) {
+                           bool own_targets, int64_t precision) {
   if (table.empty() || table.size() > (size_t)sml::DMB_MAXLAYERS)
     return std::to_string(table.size()) + " Dense layers: the persistent trainer takes 1.." +
            std::to_string((int)sml::DMB_MAXLAYERS) + " (MAX_LAYERS)";
   sml::DenseMBLayer L[sml::DMB_MAXLAYERS] = {};
   const int nl = dense_mb_table(table, L);
   return sml::dense_mb_check(L, nl, L[0].in, (int)std::min<int64_t>(batch, 1 << 30), nflat < 0 ? INT64_MAX : nflat,
-                             own_targets);
+                             own_targets, (int)std::min<int64_t>(std::max<int64_t>(precision, -1), 2));
 }
 
 // nsteps consecutive Keras steps of a Dense stack in one launch (dense_minibatch.hip); flat / m / v /
@@ -1147,7 +1147,8 @@ std::string dense_mb_check(const std::vector<std::vector<double>>& table, int64_
 at::Tensor dense_mb_train(const at::Tensor& flat, const at::Tensor& m, const at::Tensor& v, const at::Tensor& iter,
                           const std::vector<std::vector<double>>& table, const at::Tensor& x,
                           const c10::optional<at::Tensor>& y, const c10::optional<at::Tensor>& order, int64_t row0,
-                          int64_t batch, int64_t nsteps, double lr, double beta1, double beta2, double eps) {
+                          int64_t batch, int64_t nsteps, double lr, double beta1, double beta2, double eps,
+                          int64_t precision) {
   check_dev(flat, "flat", at::kFloat);
   check_dev(m, "m", at::kFloat);
   check_dev(v, "v", at::kFloat);
@@ -1155,7 +1156,7 @@ at::Tensor dense_mb_train(const at::Tensor& flat, const at::Tensor& m, const at:
   TORCH_CHECK(iter.is_cuda() && iter.scalar_type() == at::kLong && iter.numel() == 1, "iter must be a device int64[1]");
   TORCH_CHECK(flat.is_contiguous() && m.is_contiguous() && v.is_contiguous() && m.numel() == flat.numel() &&
                   v.numel() == flat.numel(), "flat / m / v must be contiguous and of one size");
-  const std::string why = dense_mb_check(table, batch, flat.numel(), y.has_value());
+  const std::string why = dense_mb_check(table, batch, flat.numel(), y.has_value(), precision);
   TORCH_CHECK(why.empty(), "dense_mb_train: ", why);
   sml::DenseMBArgs a{};
   a.nl = dense_mb_table(table, a.L);
@@ -1194,6 +1195,7 @@ at::Tensor dense_mb_train(const at::Tensor& flat, const at::Tensor& m, const at:
   a.beta2 = (float)beta2;
   a.eps = (float)eps;
   a.out = out.data_ptr<float>();
+  a.precision = (int)precision;
   SML_CHECK_HIP(sml::dense_mb_launch(a, cur_stream(x)));
   return out;
 }
@@ -1749,13 +1751,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("flat"), py::arg("m"), py::arg("v"), py::arg("iter"), py::arg("table"), py::arg("x"),
         py::arg("y") = py::none(), py::arg("order") = py::none(), py::arg("row0") = 0, py::arg("batch") = 32,
         py::arg("nsteps") = 1, py::arg("lr") = 1e-3, py::arg("beta1") = 0.9, py::arg("beta2") = 0.999,
-        py::arg("eps") = 1e-7);
-  m.def("dense_mb_check", &dense_mb_check, "empty if dense_mb_train can run the table at this batch, else the reason",
-        py::arg("table"), py::arg("batch"), py::arg("nflat") = -1, py::arg("own_targets") = false);
+        py::arg("eps") = 1e-7, py::arg("precision") = 0);
+  m.def("dense_mb_check", &dense_mb_check,
+        "empty if dense_mb_train can run the table at this batch and precision (0 fp32, 1 bf16), else the reason",
+        py::arg("table"), py::arg("batch"), py::arg("nflat") = -1, py::arg("own_targets") = false,
+        py::arg("precision") = 0);
   m.attr("DMB_MAXLAYERS") = (int)sml::DMB_MAXLAYERS;
   m.attr("DMB_MAXW") = (int)sml::DMB_MAXW;
   m.attr("DMB_MAXBATCH") = (int)sml::DMB_MAXBATCH;
   m.attr("DMB_MAXPARAMS") = (int)sml::DMB_MAXPARAMS;
+  m.attr("DMB_MAXPARAMS_BF16") = (int)sml::DMB_MAXPARAMS_BF16;
   m.attr("DMB_LDS_BYTES") = (int)sml::DMB_LDS_BYTES;
   m.def("mlp_fwd", &mlp_fwd, "dropout(act(x . W + b)) on fp32 MFMA (x float32 or uint8 scaled by 1/255)",
         py::arg("x"), py::arg("W"), py::arg("b") = py::none(), py::arg("relu") = false, py::arg("keep") = 1.0,

@@ -115,6 +115,8 @@ class Model:
         self._fused = None
         self._fused_arg: Optional[bool] = None
         self.last_fit_engine: Optional[str] = None
+        self.last_fit_precision: Optional[str] = None
+        self.minibatch_precision: Optional[str] = None
         self._acc = None
         self._pending_opt_state = None
 
@@ -170,7 +172,17 @@ class Model:
 
     # ------------------------------------------------------------------ compile
     def compile(self, optimizer="adam", loss="mean_squared_error", metrics=None, fused: Optional[bool] = None,
-                **kw) -> "Model":
+                minibatch_precision: Optional[str] = None, **kw) -> "Model":
+        """Keras ``compile``.  ``minibatch_precision`` picks the small-batch trainer's contractions:
+        ``"bf16"`` asks for bf16 MFMAs with fp32 master weights and Adam -- the persistent Dense
+        trainer (``ops.dense_persistent``) uses its bf16 kernel where the stack fits that kernel's
+        limits and its fp32 kernel otherwise (``last_fit_precision`` records which), and the
+        recognised 4-layer autoencoder is compiled with the same option; ``"fp32"`` or ``None``
+        keep fp32 (for the recognised autoencoder ``None`` follows the process default).  The
+        layer-by-layer engine ignores it."""
+        if minibatch_precision not in (None, "fp32", "bf16"):
+            raise ValueError("minibatch_precision must be 'fp32', 'bf16' or None")
+        self.minibatch_precision = minibatch_precision
         self.build()
         if isinstance(optimizer, Adam):
             self.hp = dict(lr=optimizer.lr, beta_1=optimizer.beta_1, beta_2=optimizer.beta_2,
@@ -236,7 +248,8 @@ class Model:
                          device=self.device, layer_names=names, name=self.name)
         ae.hp = dict(self.hp)
         ae.set_weights(self.fp.get())
-        ae.compile(metrics=self.metrics or (), learning_rate=self.hp["lr"])
+        ae.compile(metrics=self.metrics or (), learning_rate=self.hp["lr"],
+                   minibatch_precision=self.minibatch_precision)
         it, m, v = self.opt.state()
         if it:
             ae.backend.set_optimizer_state(it, m, v)
@@ -405,7 +418,10 @@ class Model:
         ROCm device, else the layer-by-layer loop; ``"persistent"`` insists on the persistent
         trainer (``ValueError`` with the reason if it cannot run); ``"layers"`` runs the layer
         loop for this call, also on the recognised autoencoder (whose fused backend then receives
-        the trained state), as ``compile(fused=False)`` does for every call.  ``last_fit_engine`` records the choice."""
+        the trained state), as ``compile(fused=False)`` does for every call.  ``last_fit_engine`` records the choice,
+        and ``last_fit_precision`` the persistent trainer's kernel (``"bf16"`` when
+        ``compile(minibatch_precision="bf16")`` asked for it and the stack fits the bf16 kernel, else
+        ``"fp32"``; ``None`` when another engine ran)."""
         if engine not in ("auto", "persistent", "layers"):
             raise ValueError(f"engine must be 'auto', 'persistent' or 'layers', not {engine!r}")
         if not self.compiled:
@@ -417,6 +433,7 @@ class Model:
             if y is not None and y is not x:
                 raise ValueError("autoencoder fit expects y == x")
             self.last_fit_engine = "fused"
+            self.last_fit_precision = None
             hist = self._fused.fit(x, epochs=epochs, batch_size=batch_size, verbose=verbose, callbacks=callbacks,
                                    validation_data=validation_data, shuffle=shuffle,
                                    steps_per_epoch=steps_per_epoch, seed=seed, initial_epoch=initial_epoch)
@@ -437,6 +454,7 @@ class Model:
             if engine == "persistent":
                 raise ValueError(f"engine='persistent' cannot run: {why}")
         self.last_fit_engine = "layers"
+        self.last_fit_precision = None
         hist = History()
         cbs = [hist] + list(callbacks or [])
         for cb in cbs:
@@ -530,6 +548,12 @@ class Model:
         self.last_fit_engine = "persistent"
         B = int(batch_size)
         stream = isinstance(x, Stream)
+        # bf16 only where it was asked for and the stack fits the bf16 kernel; never an error
+        own_targets = not stream and y is not None and y is not x
+        prec = "fp32"
+        if self.minibatch_precision == "bf16" and dpers.supports(self, B, own_targets=own_targets, precision="bf16")[0]:
+            prec = "bf16"
+        self.last_fit_precision = prec
         if not stream:
             xd = self._prep_x(x).float()
             yd = None if (y is None or y is x) else self._prep_y(y).float()
@@ -561,7 +585,7 @@ class Model:
                     if cap is not None:
                         k = min(k, cap - steps)
                     maybe_inject_range(gstep, gstep + k, 0)
-                    results.append(dpers.train_steps(self, xs, None, B, k, 0, None))
+                    results.append(dpers.train_steps(self, xs, None, B, k, 0, None, precision=prec))
                     used = min(int(xs.shape[0]), k * B)
                     weights += [B] * (k - 1) + [used - B * (k - 1)]
                     rows += used
@@ -576,7 +600,7 @@ class Model:
                     order = torch.from_numpy(rng.permutation(n).astype(np.int32)).to(self.device)
                 if steps > 0:
                     maybe_inject_range(gstep, gstep + steps, 0)
-                    results.append(dpers.train_steps(self, xd, yd, B, steps, 0, order))
+                    results.append(dpers.train_steps(self, xd, yd, B, steps, 0, order, precision=prec))
                 rows = min(n, steps * B)
                 weights = [B] * (steps - 1) + [rows - B * (steps - 1)] if steps > 0 else []
                 gstep += steps
