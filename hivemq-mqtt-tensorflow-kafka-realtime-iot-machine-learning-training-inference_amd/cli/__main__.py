@@ -21,6 +21,7 @@ Commands (reference script in parentheses):
   serve        <servers> <topic> <result_topic> <model-file> [--replicas W --replica-index R]
                long-running shard-by-key anomaly scorer (one replica per GPU; model-predictions Deployment)
   fleet        <csv|synthetic> [--models N] [--epochs E]   one AE per car, all trained at once on one GPU
+               [--layers 64,16,64 [--precision bf16]]      the same for the Dense stack `cardata-v3 --layers` builds
 """
 from __future__ import annotations
 

@@ -7,7 +7,13 @@ key with the same Keras-batch semantics, all models at once on one GPU
 (``ops/ae_fleet.py``).  It then writes every model as a Keras HDF5 file plus an
 ``index.json`` {name -> file, keys, final loss}.
 
+``--layers 64,16,64`` trains the Dense stack ``cardata-v3 --layers`` builds (18 in, 18 out, tanh /
+relu alternating, relu last) instead, one persistent workgroup per model (``ops/dense_fleet.py``),
+on rows normalised once on the host; every ``.h5`` is one ``serve --model dense`` accepts and
+``index.json`` also records ``layers``, ``engine`` and ``precision``.
+
   fleet <csv|synthetic> [--models N] [--epochs E] [--batch 32] [--lr 1e-3] [--out DIR]
+        [--layers 64,16,64 [--precision fp32|bf16]]
 """
 from __future__ import annotations
 
@@ -31,7 +37,15 @@ def parse_args(argv: Sequence[str]):
     p.add_argument("--seed", type=int, default=0)
     p.add_argument("--synthetic-rows", type=int, default=1 << 20)
     p.add_argument("--synthetic-devices", type=int, default=1000)
-    return p.parse_args(list(argv))
+    p.add_argument("--layers", default=None,
+                   help="hidden widths of a Dense stack, e.g. 64,16,64 (18 in, 18 out; tanh / relu alternate, relu "
+                        "last): trains a fleet of such stacks on the persistent Dense trainer")
+    p.add_argument("--precision", default=None, choices=["fp32", "bf16"],
+                   help="with --layers: the trainer's contractions, fp32 (default) or bf16 MFMAs")
+    ns = p.parse_args(list(argv))
+    if ns.precision is not None and ns.layers is None:
+        p.error("--precision goes with --layers")
+    return ns
 
 
 def model_name(members, i: int, used=None) -> str:
@@ -62,8 +76,85 @@ def training_rows(ns):
     return raw, keys
 
 
+INDEX_META = ("layers", "engine", "precision")   # keys of index.json beside the models' names (--layers)
+
+
+def build_index(names, members, losses, layers=None, precision=None) -> dict:
+    """``index.json``: name -> {file, keys, loss}; for a ``--layers`` fleet also the stack's hidden
+    widths, the engine that trained it and its precision."""
+    index = {name: {"file": name + ".h5", "keys": [str(k) for k in members[i]], "loss": losses[i]}
+             for i, name in enumerate(names)}
+    if layers is not None:
+        index.update(layers=[int(w) for w in layers], engine="persistent", precision=precision or "fp32")
+    return index
+
+
+def dense_stack(hidden, seed: int, lr: float, device="cpu", precision=None, features: int = 18):
+    """The ``cardata-v3 --layers`` stack: features -> hidden widths -> features, tanh / relu
+    alternating, relu last, compiled for MSE."""
+    from .. import nn
+    from ..nn.model import Adam
+    widths = list(hidden) + [features]
+    acts = ["tanh" if i % 2 == 0 else "relu" for i in range(len(widths))]
+    acts[-1] = "relu"
+    model = nn.Sequential([nn.Dense(u, activation=a, input_shape=(features,) if i == 0 else None)
+                           for i, (u, a) in enumerate(zip(widths, acts))], device=device, seed=seed)
+    model.compile(optimizer=Adam(learning_rate=lr), loss="mean_squared_error", metrics=["accuracy"],
+                  minibatch_precision=precision)
+    return model
+
+
+def _main_layers(ns) -> int:
+    import numpy as np
+    import torch
+
+    from ..data.cardata import normalize_affine
+    from ..ops.ae_fleet import ragged_rings_by_key
+    from ..ops.dense_fleet import DenseFleet
+    from .cardata_autoencoder import _hidden_widths
+
+    hidden = _hidden_widths(ns.layers)
+    precision = ns.precision or "fp32"
+    raw, keys = training_rows(ns)
+    scale, shift = normalize_affine()
+    rows = (raw.astype(np.float64) * scale + shift).astype(np.float32)     # normalize_fn, once
+    flat, table, members = ragged_rings_by_key(rows, keys, batch=ns.batch, n_models=ns.models)
+    M = len(members)
+    ok, why = DenseFleet.supports(dense_stack(hidden, ns.seed, ns.lr, features=raw.shape[1]), ns.batch, M, precision)
+    if not ok:
+        raise SystemExit(f"fleet --layers {ns.layers}: {why}")
+    dev = torch.device(ns.device)
+    fleet = DenseFleet.from_seeds(lambda s: dense_stack(hidden, s, ns.lr, features=raw.shape[1]),
+                                  [ns.seed + i for i in range(M)], dev, precision=precision)
+    fleet.attach_ragged(torch.from_numpy(flat).to(dev), ns.batch, table)
+    steps = fleet.epoch_steps()
+    D = raw.shape[1]
+    print(f"fleet: {M} models {D}-{'-'.join(str(w) for w in hidden)}-{D} ({precision}), {len(flat)} rows, "
+          f"{int(steps.min())}-{int(steps.max())} steps of {ns.batch} rows per model per epoch", flush=True)
+    ms = []
+    for ep in range(ns.epochs):
+        fleet.reset_metrics()
+        fleet.train_epoch()
+        ms = fleet.read_metrics()
+        losses = np.array([m["loss"] for m in ms])
+        print(f"Epoch {ep + 1}/{ns.epochs} - loss mean {losses.mean():.4f} min {losses.min():.4f} "
+              f"max {losses.max():.4f}", flush=True)
+    os.makedirs(ns.out, exist_ok=True)
+    used = set(INDEX_META)
+    names = [model_name(members, i, used) for i in range(M)]
+    for i, name in enumerate(names):
+        fleet.model(i, device="cpu").save(os.path.join(ns.out, name + ".h5"))
+    index = build_index(names, members, [ms[i]["loss"] if ms else None for i in range(M)], hidden, precision)
+    with open(os.path.join(ns.out, "index.json"), "w") as f:
+        json.dump(index, f, indent=1)
+    print(f"wrote {M} models to {ns.out}", flush=True)
+    return 0
+
+
 def main(argv: Sequence[str]) -> int:
     ns = parse_args(argv)
+    if ns.layers:
+        return _main_layers(ns)
     import numpy as np
     import torch
 

@@ -493,6 +493,26 @@ struct DenseMBPlanBF16 {
 DenseMBPlanBF16 dense_mb_plan_bf16(const DenseMBLayer* L, int nl, int D, bool own_targets);
 hipError_t dense_mb_launch_bf16(const DenseMBArgs& args, hipStream_t stream);   // args checked by dense_mb_launch
 
+// ---- fleets: M models of ONE architecture, workgroup b trains model sched[b] (both kernel files) ----
+// The fleet entries rebase DenseMBArgs once per workgroup from the model's descriptor and then run
+// the single-model body, so a member's bits are those of the model trained alone.  No workgroup
+// waits on another; a fleet of more workgroups than CUs runs in rounds.
+struct DenseMBFleetModel {
+  int64_t first_row, rows;   // the model's slice of x[N, D] (and of y[N, O], order[N]); order holds indices local to it
+  int64_t row0;              // first sample of this launch inside the slice
+  int nsteps;                // the model takes min(nsteps, ceil((rows - row0) / batch)) steps
+  float lr;
+};
+static_assert(sizeof(DenseMBFleetModel) == 32, "DenseMBFleetModel is read from a [M, 4] int64 tensor");
+// args describes the shared part: the layer table, batch, Adam constants, precision, x / y / order of
+// the whole row array, flat / m / v [M, stride] and iter [M] of the stacked state, out [M, args.nsteps, 2]
+// with args.nsteps the largest nsteps of the launch.  args.n, row0 and lr are ignored.  models and
+// sched (a permutation of 0 .. M - 1) are device arrays.
+hipError_t dense_mb_fleet_launch(DenseMBArgs args, const DenseMBFleetModel* models, const int32_t* sched, int M,
+                                 int64_t stride, hipStream_t stream);
+hipError_t dense_mb_fleet_launch_bf16(const DenseMBArgs& args, const DenseMBFleetModel* models, const int32_t* sched,
+                                      int M, int64_t stride, hipStream_t stream);   // args checked by dense_mb_fleet_launch
+
 // ---- fused MSE + categorical accuracy (loss.hip) ----
 bool mse_acc_supported(int F);
 // acc != null needs part: 2 * mse_acc_blocks(rows, F) floats of scratch (the block partials,

@@ -27,10 +27,13 @@
 //   * padded units are forced to 0 on the way forward and to 0 gradient on the way back, and a
 //     padded parameter is never updated or written, so a sigmoid's act(0) = 0.5 cannot leak.
 // The kernel waits on nothing outside the workgroup: every loop bound is known at launch.
+// That is what lets dense_mb_fleet_kernel run M models of one architecture side by side, workgroup b
+// on model sched[b] (sml_dense_fleet.h): the same body (sml_dense_mb_body.h) on rebased arguments.
 #include "sml_common.h"
 #include "sml_ops.h"
 
 #include "sml_adam.h"
+#include "sml_dense_fleet.h"
 
 #include <string>
 #include <type_traits>
@@ -147,13 +150,14 @@ struct Stage {
   float x[SE], y[SE];
 };
 
-__device__ __forceinline__ void stage_load(const DenseMBArgs& a, int O, int s, int k, int steps, Stage& st) {
+template <typename Run>
+__device__ __forceinline__ void stage_load(const DenseMBArgs& a, const Run& run, int O, int s, int k, int steps, Stage& st) {
   const int r = threadIdx.x / LPR, q = threadIdx.x % LPR;
   int rows = 0;
   int64_t pos = 0;
   if (s < steps) {
-    const int64_t base = a.row0 + (int64_t)s * a.batch;
-    const int64_t left = a.n - base;
+    const int64_t base = run.row0 + (int64_t)s * a.batch;
+    const int64_t left = run.n - base;
     const int rows_s = left < a.batch ? (int)left : a.batch;
     rows = rows_s - k * CH < CH ? rows_s - k * CH : CH;
     pos = base + k * CH + r;
@@ -161,24 +165,25 @@ __device__ __forceinline__ void stage_load(const DenseMBArgs& a, int O, int s, i
   const bool rv = r < rows;
   int64_t src = 0;
   if (rv) {
-    src = a.order ? (int64_t)a.order[pos] : pos;
-    src = src < 0 ? 0 : src >= a.n ? a.n - 1 : src;
+    src = run.order ? (int64_t)run.order[pos] : pos;
+    src = src < 0 ? 0 : src >= run.n ? run.n - 1 : src;
   }
 #pragma unroll
   for (int e = 0; e < SE; ++e) {
     const int c = q + LPR * e;
-    st.x[e] = (rv && c < a.D) ? a.x[src * a.ldx + c] : 0.0f;
-    st.y[e] = (a.y != nullptr && rv && c < O) ? a.y[src * a.ldy + c] : 0.0f;
+    st.x[e] = (rv && c < a.D) ? run.x[src * a.ldx + c] : 0.0f;
+    st.y[e] = (run.y != nullptr && rv && c < O) ? run.y[src * a.ldy + c] : 0.0f;
   }
 }
 
-__device__ __forceinline__ void stage_store(float* S, const DenseMBArgs& a, int op, const Stage& st) {
+template <typename Run>
+__device__ __forceinline__ void stage_store(float* S, const DenseMBArgs& a, const Run& run, int op, const Stage& st) {
   const int r = threadIdx.x / LPR, q = threadIdx.x % LPR;
 #pragma unroll
   for (int e = 0; e < SE; ++e) {
     const int c = q + LPR * e;
     if (c < a.P.dp) S[a.P.la0 + r * a.P.dp + c] = st.x[e];
-    if (a.y != nullptr && c < op) S[a.P.lyt + r * op + c] = st.y[e];
+    if (run.y != nullptr && c < op) S[a.P.lyt + r * op + c] = st.y[e];
   }
 }
 
@@ -278,166 +283,17 @@ __device__ __forceinline__ void tile_params(float* S, const Tile& T, const Dense
 }
 
 __global__ __launch_bounds__(NT) void dense_mb_kernel(const DenseMBArgs a) {
-  extern __shared__ __attribute__((aligned(16))) float S[];
-  __shared__ DenseMBLayer sL[DMB_MAXLAYERS];
-  __shared__ DenseMBLayerPlan sP[DMB_MAXLAYERS];
-  const int tid = threadIdx.x, nl = a.nl;
-  if (tid == 0) {
-#pragma unroll
-    for (int l = 0; l < DMB_MAXLAYERS; ++l) {
-      sL[l] = a.L[l];
-      sP[l] = a.P.L[l];
-    }
-  }
-  for (int i = a.P.wimg0 + tid; i < a.P.wimg1; i += NT) S[i] = 0.0f;
-  if (tid < 3) S[a.P.lstat + STAT_TOT + tid] = 0.0f;
-  __syncthreads();
+  const DenseMBArgs& run = a;
+#include "sml_dense_mb_body.h"
+}
 
-  // ---- the tiles this thread owns: tid, tid + NT, ... ----
-  Tile T[DMB_TPT];
-#pragma unroll
-  for (int u = 0; u < DMB_TPT; ++u) {
-    Tile& t = T[u];
-    const int id = tid + u * NT;
-    t.l = -1;
-    t.iq = t.jq = 0;
-    if (id < a.P.ntiles) {
-      for (int l = 0; l < nl; ++l)
-        if (id >= sP[l].tile0) t.l = l;
-      const int k = id - sP[t.l].tile0, nq = sP[t.l].up >> 2;
-      t.iq = k / nq;
-      t.jq = k - t.iq * nq;
-    }
-#pragma unroll
-    for (int e = 0; e < 4; ++e) t.m[e] = t.v[e] = f32x4{0.f, 0.f, 0.f, 0.f};
-    t.mb = t.vb = f32x4{0.f, 0.f, 0.f, 0.f};
-    tile_params<true>(
-        S, t, sL, sP,
-        [&](int e, int c, unsigned f, float* p) {
-          *p = a.flat[f];
-          t.m[e][c] = a.m[f];
-          t.v[e][c] = a.v[f];
-        },
-        [&](int c, unsigned f, float* p) {
-          *p = a.flat[f];
-          t.mb[c] = a.m[f];
-          t.vb[c] = a.v[f];
-        });
-  }
-
-  const int64_t it0 = *a.iter;
-  const int O = sL[nl - 1].units, op = sP[nl - 1].up;
-  const int64_t avail = a.n - a.row0;
-  const int64_t maxsteps = avail > 0 ? (avail + a.batch - 1) / a.batch : 0;
-  const int steps = (int)(maxsteps < a.nsteps ? maxsteps : a.nsteps);
-
-  Stage st;
-  stage_load(a, O, 0, 0, steps, st);
-  for (int s = 0; s < steps; ++s) {
-    const int64_t left = avail - (int64_t)s * a.batch;
-    const int rows_s = left < a.batch ? (int)left : a.batch;
-    const int chunks = (rows_s + CH - 1) / CH;
-    const float inv_rows = 1.0f / (float)rows_s, inv_n = 1.0f / ((float)rows_s * (float)O);
-#pragma unroll
-    for (int u = 0; u < DMB_TPT; ++u) {
-#pragma unroll
-      for (int e = 0; e < 4; ++e) T[u].g[e] = f32x4{0.f, 0.f, 0.f, 0.f};
-      T[u].gb = f32x4{0.f, 0.f, 0.f, 0.f};
-    }
-    for (int k = 0; k < chunks; ++k) {
-      const int rows = rows_s - k * CH < CH ? rows_s - k * CH : CH;
-      stage_store(S, a, op, st);
-      if (k + 1 < chunks) stage_load(a, O, s, k + 1, steps, st);
-      else stage_load(a, O, s + 1, 0, steps, st);
-      __syncthreads();
-      // ---- forward ----
-      for (int l = 0; l < nl; ++l) {
-        const int la_prev = l == 0 ? a.P.la0 : sP[l - 1].la;
-        by_row_tile(rows, sP[l].up >> 2, [&](auto rt) { fwd_layer<decltype(rt)::value>(S, sL[l], sP[l], la_prev, rows); });
-        __syncthreads();
-      }
-      loss_phase(S, sL, sP, nl, a.P.lyt, a.P.lstat, rows, inv_n, inv_rows);
-      __syncthreads();
-      // ---- backward ----
-      for (int l = nl - 1; l >= 1; --l) {
-        by_row_tile(rows, sP[l].ip >> 2,
-                    [&](auto rt) { bwd_layer<decltype(rt)::value>(S, sP[l], sL[l - 1], sP[l - 1], rows, inv_rows); });
-        __syncthreads();
-      }
-      // ---- weight / bias gradients into the owners' registers, rows ascending ----
-#pragma unroll
-      for (int u = 0; u < DMB_TPT; ++u) {
-        Tile& t = T[u];
-        if (t.l < 0) continue;
-        const DenseMBLayerPlan& P = sP[t.l];
-        const float* hp = S + (t.l == 0 ? a.P.la0 : sP[t.l > 0 ? t.l - 1 : 0].la) + 4 * t.iq;
-        const float* dp = S + P.ld + 4 * t.jq;
-#pragma unroll 4
-        for (int r = 0; r < rows; ++r) {
-          const f32x4 h = ld4(hp + r * P.ip), d = ld4(dp + r * P.up);
-#pragma unroll
-          for (int e = 0; e < 4; ++e)
-#pragma unroll
-            for (int c = 0; c < 4; ++c) t.g[e][c] = fmaf(h[e], d[c], t.g[e][c]);
-          if (t.iq == 0) t.gb += d;   // only the tiles of rows 0..3 own bias elements
-        }
-      }
-      if (tid < 3) {   // the step's squared error / correct rows / penalty, rows ascending
-        float tot = S[a.P.lstat + STAT_TOT + tid];
-        for (int r = 0; r < rows; ++r) tot += S[a.P.lstat + CH * tid + r];
-        S[a.P.lstat + STAT_TOT + tid] = tot;
-      }
-      __syncthreads();
-    }
-    // ---- Adam on the owned parameters; the LDS image is updated in place ----
-    const float lr_t = adam_lr_t(a.lr, a.beta1, a.beta2, (float)(it0 + s + 1));
-#pragma unroll
-    for (int u = 0; u < DMB_TPT; ++u) {
-      Tile& t = T[u];
-      tile_params<false>(
-          S, t, sL, sP,
-          [&](int e, int c, unsigned, float* p) {
-            float mm, vv, pn;
-            adam_update(t.g[e][c], t.m[e][c], t.v[e][c], *p, lr_t, a.beta1, a.beta2, a.eps, 1.0f, mm, vv, pn);
-            t.m[e][c] = mm;
-            t.v[e][c] = vv;
-            *p = pn;
-          },
-          [&](int c, unsigned, float* p) {
-            float mm, vv, pn;
-            adam_update(t.gb[c], t.mb[c], t.vb[c], *p, lr_t, a.beta1, a.beta2, a.eps, 1.0f, mm, vv, pn);
-            t.mb[c] = mm;
-            t.vb[c] = vv;
-            *p = pn;
-          });
-    }
-    if (tid == 0) {
-      const float* tot = S + a.P.lstat + STAT_TOT;
-      a.out[2 * s] = tot[0] * inv_n + tot[2] * inv_rows;
-      a.out[2 * s + 1] = tot[1];
-    }
-    __syncthreads();
-    if (tid < 3) S[a.P.lstat + STAT_TOT + tid] = 0.0f;   // next touched after the next chunk's barriers
-  }
-
-  // ---- write the real parameters and their moments back ----
-#pragma unroll
-  for (int u = 0; u < DMB_TPT; ++u) {
-    Tile& t = T[u];
-    tile_params<true>(
-        S, t, sL, sP,
-        [&](int e, int c, unsigned f, float* p) {
-          a.flat[f] = *p;
-          a.m[f] = t.m[e][c];
-          a.v[f] = t.v[e][c];
-        },
-        [&](int c, unsigned f, float* p) {
-          a.flat[f] = *p;
-          a.m[f] = t.mb[c];
-          a.v[f] = t.vb[c];
-        });
-  }
-  if (tid == 0) *a.iter = it0 + steps;
+// Fleet entry: workgroup b trains model sched[b] of M models of one architecture (sml_dense_fleet.h).
+// The rebase happens once, before the first load; from then on this is the single-model launch, and
+// the workgroup leaves when its own model is done.
+__global__ __launch_bounds__(NT) void dense_mb_fleet_kernel(const DenseMBArgs a, const DenseMBFleetModel* __restrict__ models,
+                                                            const int32_t* __restrict__ sched, const int64_t stride) {
+  const DenseMBRun run = fleet_run(SML_DENSE_MB_SINGLE_RUN(a), a.ldx, a.ldy, models, sched, stride);
+#include "sml_dense_mb_body.h"
 }
 
 constexpr int pad4(int n) { return (n + 3) / 4 * 4; }
@@ -553,6 +409,23 @@ hipError_t dense_mb_launch(DenseMBArgs a, hipStream_t stream) {
     if (e != hipSuccess) return e;
   }
   hipLaunchKernelGGL(dense_mb_kernel, dim3(1), dim3(NT), lds, stream, a);
+  return hipGetLastError();
+}
+
+hipError_t dense_mb_fleet_launch(DenseMBArgs a, const DenseMBFleetModel* models, const int32_t* sched, int M,
+                                 int64_t stride, hipStream_t stream) {
+  const bool own_targets = a.y != nullptr;
+  if (dense_mb_check(a.L, a.nl, a.D, a.batch, stride, own_targets, a.precision)[0] != 0) return hipErrorInvalidValue;
+  if (M < 1 || a.nsteps < 1 || models == nullptr || sched == nullptr) return hipErrorInvalidValue;
+  if (a.precision == DMB_BF16) return dense_mb_fleet_launch_bf16(a, models, sched, M, stride, stream);
+  a.P = dense_mb_plan(a.L, a.nl, a.D, own_targets);
+  const size_t lds = sizeof(float) * (size_t)a.P.lds_floats;
+  if (lds > 65536) {
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(dense_mb_fleet_kernel),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL(dense_mb_fleet_kernel, dim3(M), dim3(NT), lds, stream, a, models, sched, stride);
   return hipGetLastError();
 }
 

@@ -32,11 +32,14 @@
 //     (sigmoid(0) = 0.5 cannot leak).  Every chunk computes all 32 rows: absent rows are zero inputs.
 // Every transposed read is executed by all 64 lanes of every wave (wave-uniform control flow; out-of-
 // range K pieces read a clamped address and are replaced by zeros).  The kernel synchronises with
-// __syncthreads() only and every loop bound is known at launch.
+// __syncthreads() only and every loop bound is known at launch.  dense_mb_bf16_fleet_kernel runs M models
+// of one architecture side by side, workgroup b on model sched[b] (sml_dense_fleet.h): the same body
+// (sml_dense_mb_bf16_body.h) on rebased arguments.
 #include "sml_common.h"
 #include "sml_ops.h"
 
 #include "sml_adam.h"
+#include "sml_dense_fleet.h"
 
 namespace sml {
 namespace {
@@ -144,13 +147,14 @@ struct Stage {
   float x[SE], y[SE];
 };
 
-__device__ __forceinline__ void stage_load(const DenseMBArgs& a, int O, int s, int k, int steps, Stage& st) {
+template <typename Run>
+__device__ __forceinline__ void stage_load(const DenseMBArgs& a, const Run& run, int O, int s, int k, int steps, Stage& st) {
   const int r = threadIdx.x / LPR, q = threadIdx.x % LPR;
   int rows = 0;
   int64_t pos = 0;
   if (s < steps) {
-    const int64_t base = a.row0 + (int64_t)s * a.batch;
-    const int64_t left = a.n - base;
+    const int64_t base = run.row0 + (int64_t)s * a.batch;
+    const int64_t left = run.n - base;
     const int rows_s = left < a.batch ? (int)left : a.batch;
     rows = rows_s - k * CH < CH ? rows_s - k * CH : CH;
     pos = base + k * CH + r;
@@ -158,18 +162,19 @@ __device__ __forceinline__ void stage_load(const DenseMBArgs& a, int O, int s, i
   const bool rv = r < rows;
   int64_t src = 0;
   if (rv) {
-    src = a.order ? (int64_t)a.order[pos] : pos;
-    src = src < 0 ? 0 : src >= a.n ? a.n - 1 : src;
+    src = run.order ? (int64_t)run.order[pos] : pos;
+    src = src < 0 ? 0 : src >= run.n ? run.n - 1 : src;
   }
 #pragma unroll
   for (int e = 0; e < SE; ++e) {
     const int c = q + LPR * e;
-    st.x[e] = (rv && c < a.D) ? a.x[src * a.ldx + c] : 0.0f;
-    st.y[e] = (a.y != nullptr && rv && c < O) ? a.y[src * a.ldy + c] : 0.0f;
+    st.x[e] = (rv && c < a.D) ? run.x[src * a.ldx + c] : 0.0f;
+    st.y[e] = (run.y != nullptr && rv && c < O) ? run.y[src * a.ldy + c] : 0.0f;
   }
 }
 
-__device__ __forceinline__ void stage_store(lds_t* S, const DenseMBArgs& a, const DenseMBPlanBF16& P, int op, const Stage& st) {
+template <typename Run>
+__device__ __forceinline__ void stage_store(lds_t* S, const Run& run, const DenseMBPlanBF16& P, int op, const Stage& st) {
   const int r = threadIdx.x / LPR, q = threadIdx.x % LPR;
   float* xr = fptr(S, P.la0) + r * P.xs;
   unsigned short* xb = reinterpret_cast<unsigned short*>(S + P.lxb) + r * P.xbs;
@@ -181,7 +186,7 @@ __device__ __forceinline__ void stage_store(lds_t* S, const DenseMBArgs& a, cons
       xr[c] = st.x[e];
       xb[c] = to_bf16(st.x[e]);
     }
-    if (a.y != nullptr && c < op) yr[c] = st.y[e];
+    if (run.y != nullptr && c < op) yr[c] = st.y[e];
   }
 }
 
@@ -258,193 +263,18 @@ __device__ __forceinline__ bool tile_of(int info, TilePos& t) {
 }
 
 __global__ __launch_bounds__(NT) void dense_mb_bf16_kernel(const DenseMBArgs a, const DenseMBPlanBF16 P) {
-  extern __shared__ __attribute__((aligned(16))) lds_t S[];
-  __shared__ DenseMBLayer sL[DMB_MAXLAYERS];
-  __shared__ DenseMBLayerPlanBF16 sP[DMB_MAXLAYERS];
-  const int tid = threadIdx.x, nl = a.nl;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63, c = lane & 15, g = lane >> 4;
-  if (tid == 0) {
-#pragma unroll
-    for (int l = 0; l < DMB_MAXLAYERS; ++l) {
-      sL[l] = a.L[l];
-      sP[l] = P.L[l];
-    }
-  }
-  if (tid < P.ntiles) {   // tile table: layer, input block, unit block (unit blocks fastest)
-    int l = 0;
-    for (int k = 1; k < nl; ++k)
-      if (tid >= P.L[k].tile0) l = k;
-    const int k = tid - P.L[l].tile0, nj = P.L[l].up >> 4;
-    reinterpret_cast<int*>(S + P.ltile)[tid] = (l << 16) | ((k / nj) << 8) | (k % nj);
-  }
-  if (tid < 3) fptr(S, P.lstat)[STAT_TOT + tid] = 0.0f;
-  __syncthreads();
+  const DenseMBArgs& run = a;
+#include "sml_dense_mb_bf16_body.h"
+}
 
-  // ---- the tiles this wave owns: fp32 masters and moments into registers, bf16 image into LDS ----
-  f32x4 Tw[SLOTS], Tg[SLOTS], Tm[SLOTS], Tv[SLOTS];
-  int ti[SLOTS];
-#pragma unroll
-  for (int u = 0; u < SLOTS; ++u) {
-    const int id = wave + NW * u;
-    ti[u] = id < P.ntiles ? __builtin_amdgcn_readfirstlane(reinterpret_cast<const int*>(S + P.ltile)[id]) : -1;
-  }
-#pragma unroll
-  for (int u = 0; u < SLOTS; ++u) {
-    Tw[u] = Tg[u] = Tm[u] = Tv[u] = f32x4{0.f, 0.f, 0.f, 0.f};
-    TilePos t;
-    if (!tile_of(ti[u], t)) continue;
-    const DenseMBLayer& L = sL[t.l];
-    const int j = t.j0 + c;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const int i = t.i0 + 4 * g + e;
-      if (i < L.in && j < L.units) {
-        const unsigned f = (unsigned)(L.w_off + i * L.units + j);
-        Tw[u][e] = a.flat[f];
-        Tm[u][e] = a.m[f];
-        Tv[u][e] = a.v[f];
-      }
-    }
-    *reinterpret_cast<bf16x4*>(S + sP[t.l].lw + 2 * (j * sP[t.l].ws + t.i0 + 4 * g)) = pack4(Tw[u]);
-  }
-  // biases: thread (layer tid / 128 + 4k, unit tid % 128); state b, m, v, gradient = 4 x [up] fp32
-  for (int l = tid >> 7; l < nl; l += NT / DMB_MAXW) {
-    const int j = tid & (DMB_MAXW - 1), up = sP[l].up;
-    if (j >= up) continue;
-    const bool real = sL[l].has_bias && j < sL[l].units;
-    const unsigned f = (unsigned)(sL[l].b_off + j);
-    float* bs = fptr(S, sP[l].lb);
-    bs[j] = real ? a.flat[f] : 0.0f;
-    bs[up + j] = real ? a.m[f] : 0.0f;
-    bs[2 * up + j] = real ? a.v[f] : 0.0f;
-    bs[3 * up + j] = 0.0f;
-  }
-
-  const int64_t it0 = *a.iter;
-  const int O = sL[nl - 1].units, op = sP[nl - 1].up;
-  const int64_t avail = a.n - a.row0;
-  const int64_t maxsteps = avail > 0 ? (avail + a.batch - 1) / a.batch : 0;
-  const int steps = (int)(maxsteps < a.nsteps ? maxsteps : a.nsteps);
-
-  Stage st;
-  stage_load(a, O, 0, 0, steps, st);
-  for (int s = 0; s < steps; ++s) {
-    const int64_t left = avail - (int64_t)s * a.batch;
-    const int rows_s = left < a.batch ? (int)left : a.batch;
-    const int chunks = (rows_s + CH - 1) / CH;
-    const float inv_rows = 1.0f / (float)rows_s, inv_n = 1.0f / ((float)rows_s * (float)O);
-    for (int k = 0; k < chunks; ++k) {
-      const int rows = rows_s - k * CH < CH ? rows_s - k * CH : CH;
-      stage_store(S, a, P, op, st);
-      if (k + 1 < chunks) stage_load(a, O, s, k + 1, steps, st);
-      else stage_load(a, O, s + 1, 0, steps, st);
-      __syncthreads();
-      // ---- forward ----
-      for (int l = 0; l < nl; ++l) {
-        fwd_layer(S, a.L[l], P.L[l], l == 0 ? P.lxb : P.L[l - 1].lhb, l == 0 ? P.xbs : P.L[l - 1].bs, l == nl - 1, wave, c, g);
-        __syncthreads();
-      }
-      loss_phase(S, sL, sP, nl, P.lyt, P.ys, P.lstat, rows, inv_n, inv_rows);
-      __syncthreads();
-      // ---- backward ----
-      for (int l = nl - 1; l >= 1; --l) {
-        bwd_layer(S, P.L[l], a.L[l - 1], P.L[l - 1], rows, inv_rows, wave, c, g);
-        __syncthreads();
-      }
-      // ---- weight gradients into the owners' registers: dW[i][j] += sum_r h^T[i][r] dz[r][j] ----
-#pragma unroll
-      for (int u = 0; u < SLOTS; ++u) {
-        TilePos t;
-        if (!tile_of(ti[u], t)) continue;
-        const int lp = t.l > 0 ? t.l - 1 : 0;
-        const int lh = t.l == 0 ? P.lxb : P.L[lp].lhb, sh = t.l == 0 ? P.xbs : P.L[lp].bs;
-        const s16x8 ha = tr8(S, lh, 2 * sh, 0, CH, t.i0, c, g);
-        const s16x8 db = tr8(S, P.L[t.l].ld, 2 * P.L[t.l].bs, 0, CH, t.j0, c, g);
-        Tg[u] = mma(ha, db, Tg[u]);
-      }
-      // ---- bias gradients: fp32 column sums of the unrounded dz, rows ascending ----
-      for (int l = tid >> 7; l < nl; l += NT / DMB_MAXW) {
-        const int j = tid & (DMB_MAXW - 1), up = sP[l].up;
-        if (j >= up || !sL[l].has_bias) continue;
-        const float* dp = fptr(S, sP[l].la) + j;
-        float* gb = fptr(S, sP[l].lb) + 3 * up + j;
-        float sum = *gb;
-        for (int r = 0; r < CH; ++r) sum += dp[r * sP[l].hs];
-        *gb = sum;
-      }
-      if (tid < 3) {   // the step's squared error / correct rows / penalty, rows ascending
-        float* stt = fptr(S, P.lstat);
-        float tot = stt[STAT_TOT + tid];
-        for (int r = 0; r < rows; ++r) tot += stt[CH * tid + r];
-        stt[STAT_TOT + tid] = tot;
-      }
-      __syncthreads();
-    }
-    // ---- Adam on the owned masters; the bf16 image is re-derived from them ----
-    const float lr_t = adam_lr_t(a.lr, a.beta1, a.beta2, (float)(it0 + s + 1));
-#pragma unroll
-    for (int u = 0; u < SLOTS; ++u) {
-      TilePos t;
-      if (!tile_of(ti[u], t)) continue;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        float mm, vv, pn;
-        adam_update(Tg[u][e], Tm[u][e], Tv[u][e], Tw[u][e], lr_t, a.beta1, a.beta2, a.eps, 1.0f, mm, vv, pn);
-        Tm[u][e] = mm;
-        Tv[u][e] = vv;
-        Tw[u][e] = pn;
-      }
-      Tg[u] = f32x4{0.f, 0.f, 0.f, 0.f};
-      *reinterpret_cast<bf16x4*>(S + P.L[t.l].lw + 2 * ((t.j0 + c) * P.L[t.l].ws + t.i0 + 4 * g)) = pack4(Tw[u]);
-    }
-    for (int l = tid >> 7; l < nl; l += NT / DMB_MAXW) {
-      const int j = tid & (DMB_MAXW - 1), up = sP[l].up;
-      if (j >= up) continue;
-      float* bs = fptr(S, sP[l].lb);
-      float mm, vv, pn;
-      adam_update(bs[3 * up + j], bs[up + j], bs[2 * up + j], bs[j], lr_t, a.beta1, a.beta2, a.eps, 1.0f, mm, vv, pn);
-      bs[j] = pn;
-      bs[up + j] = mm;
-      bs[2 * up + j] = vv;
-      bs[3 * up + j] = 0.0f;
-    }
-    if (tid == 0) {
-      const float* tot = fptr(S, P.lstat) + STAT_TOT;
-      a.out[2 * s] = tot[0] * inv_n + tot[2] * inv_rows;
-      a.out[2 * s + 1] = tot[1];
-    }
-    __syncthreads();
-    if (tid < 3) fptr(S, P.lstat)[STAT_TOT + tid] = 0.0f;   // next touched after the next chunk's barriers
-  }
-
-  // ---- write the real parameters and their moments back ----
-#pragma unroll
-  for (int u = 0; u < SLOTS; ++u) {
-    TilePos t;
-    if (!tile_of(ti[u], t)) continue;
-    const DenseMBLayer& L = sL[t.l];
-    const int j = t.j0 + c;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const int i = t.i0 + 4 * g + e;
-      if (i < L.in && j < L.units) {
-        const unsigned f = (unsigned)(L.w_off + i * L.units + j);
-        a.flat[f] = Tw[u][e];
-        a.m[f] = Tm[u][e];
-        a.v[f] = Tv[u][e];
-      }
-    }
-  }
-  for (int l = tid >> 7; l < nl; l += NT / DMB_MAXW) {
-    const int j = tid & (DMB_MAXW - 1), up = sP[l].up;
-    if (!sL[l].has_bias || j >= sL[l].units) continue;
-    const unsigned f = (unsigned)(sL[l].b_off + j);
-    const float* bs = fptr(S, sP[l].lb);
-    a.flat[f] = bs[j];
-    a.m[f] = bs[up + j];
-    a.v[f] = bs[2 * up + j];
-  }
-  if (tid == 0) *a.iter = it0 + steps;
+// Fleet entry: workgroup b trains model sched[b] of M models of one architecture (sml_dense_fleet.h);
+// rebased once before the first load, then the single-model launch.  Nothing outside the workgroup
+// is waited on.
+__global__ __launch_bounds__(NT) void dense_mb_bf16_fleet_kernel(const DenseMBArgs a, const DenseMBPlanBF16 P,
+                                                                 const DenseMBFleetModel* __restrict__ models,
+                                                                 const int32_t* __restrict__ sched, const int64_t stride) {
+  const DenseMBRun run = fleet_run(SML_DENSE_MB_SINGLE_RUN(a), a.ldx, a.ldy, models, sched, stride);
+#include "sml_dense_mb_bf16_body.h"
 }
 
 constexpr int pad16(int n) { return (n + 15) / 16 * 16; }
@@ -519,6 +349,20 @@ hipError_t dense_mb_launch_bf16(const DenseMBArgs& a, hipStream_t stream) {
     if (e != hipSuccess) return e;
   }
   hipLaunchKernelGGL(dense_mb_bf16_kernel, dim3(1), dim3(NT), lds, stream, a, P);
+  return hipGetLastError();
+}
+
+hipError_t dense_mb_fleet_launch_bf16(const DenseMBArgs& a, const DenseMBFleetModel* models, const int32_t* sched, int M,
+                                      int64_t stride, hipStream_t stream) {
+  const DenseMBPlanBF16 P = dense_mb_plan_bf16(a.L, a.nl, a.D, a.y != nullptr);
+  if (P.ntiles > DMB_TILES_BF16 || M < 1) return hipErrorInvalidValue;
+  const size_t lds = (size_t)P.lds_bytes;
+  if (lds > 65536) {
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(dense_mb_bf16_fleet_kernel),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL(dense_mb_bf16_fleet_kernel, dim3(M), dim3(NT), lds, stream, a, P, models, sched, stride);
   return hipGetLastError();
 }
 

@@ -1200,6 +1200,96 @@ at::Tensor dense_mb_train(const at::Tensor& flat, const at::Tensor& m, const at:
   return out;
 }
 
+// One launch for a fleet of M Dense stacks of one architecture, workgroup b training model sched[b]
+// (the fleet entries of dense_minibatch.hip / dense_minibatch_bf16.hip).  flat / m / v [M, stride] and
+// iter [M] are updated in place.  models: HOST int64 [M, 4], the rows being DenseMBFleetModel
+// {first_row, rows, row0, nsteps | lr bits << 32}; sched: HOST int32 [M], a permutation.  Both are
+// checked here and copied to the device.  Returns [M, S, 2] with S the largest nsteps; the rows a
+// model does not reach stay zero.
+at::Tensor dense_mb_train_fleet(const at::Tensor& flat, const at::Tensor& m, const at::Tensor& v, const at::Tensor& iter,
+                                const std::vector<std::vector<double>>& table, const at::Tensor& x,
+                                const c10::optional<at::Tensor>& y, const c10::optional<at::Tensor>& order,
+                                const at::Tensor& models, const at::Tensor& sched, int64_t batch, double beta1,
+                                double beta2, double eps, int64_t precision) {
+  check_dev(flat, "flat", at::kFloat);
+  check_dev(m, "m", at::kFloat);
+  check_dev(v, "v", at::kFloat);
+  check_dev(x, "x", at::kFloat);
+  TORCH_CHECK(flat.dim() == 2 && flat.size(0) >= 1 && flat.is_contiguous() && m.is_contiguous() && v.is_contiguous() &&
+                  m.sizes() == flat.sizes() && v.sizes() == flat.sizes(),
+              "flat / m / v must be contiguous [M, stride] tensors of one shape, M >= 1");
+  const int64_t M = flat.size(0), stride = flat.size(1);
+  TORCH_CHECK(M < (1 << 24), "a fleet of ", M, " models: the limit is ", (1 << 24) - 1);
+  TORCH_CHECK(iter.is_cuda() && iter.scalar_type() == at::kLong && iter.is_contiguous() && iter.numel() == M,
+              "iter must be a device int64[", M, "]");
+  // stride >= nflat: every parameter offset of the table lies inside a model's segment
+  const std::string why = dense_mb_check(table, batch, stride, y.has_value(), precision);
+  TORCH_CHECK(why.empty(), "dense_mb_train_fleet: ", why);
+  sml::DenseMBArgs a{};
+  a.nl = dense_mb_table(table, a.L);
+  a.D = a.L[0].in;
+  const int O = a.L[a.nl - 1].units;
+  TORCH_CHECK(x.dim() == 2 && x.size(1) == a.D && (x.size(1) == 1 || x.stride(1) == 1), "x must be [N, ", a.D,
+              "] rows with contiguous features");
+  const int64_t N = x.size(0);
+  if (y.has_value()) {
+    check_dev(*y, "y", at::kFloat);
+    TORCH_CHECK(y->dim() == 2 && y->size(0) == N && y->size(1) == O && (y->size(1) == 1 || y->stride(1) == 1),
+                "y must be [N, ", O, "] rows with contiguous features");
+  }
+  if (order.has_value()) {
+    TORCH_CHECK(order->is_cuda() && order->scalar_type() == at::kInt && order->is_contiguous() && order->numel() == N,
+                "order must be a device int32 [N] of indices local to each model's rows");
+  }
+  TORCH_CHECK(!models.is_cuda() && models.scalar_type() == at::kLong && models.is_contiguous() && models.dim() == 2 &&
+                  models.size(0) == M && models.size(1) == 4,
+              "models must be a host int64 [", M, ", 4] tensor of descriptors");
+  TORCH_CHECK(!sched.is_cuda() && sched.scalar_type() == at::kInt && sched.is_contiguous() && sched.numel() == M,
+              "sched must be a host int32 [", M, "] permutation");
+  const auto* fm = reinterpret_cast<const sml::DenseMBFleetModel*>(models.data_ptr<int64_t>());
+  int64_t S = 0;
+  for (int64_t b = 0; b < M; ++b) {
+    TORCH_CHECK(fm[b].rows >= 1 && fm[b].first_row >= 0 && fm[b].first_row <= N - fm[b].rows, "model ", b, ": rows ",
+                fm[b].first_row, " .. ", fm[b].first_row, " + ", fm[b].rows, " lie outside the ", N, " rows of x");
+    TORCH_CHECK(fm[b].row0 >= 0 && fm[b].row0 < fm[b].rows, "model ", b, ": row0 ", fm[b].row0, " is outside its ",
+                fm[b].rows, " rows");
+    TORCH_CHECK(fm[b].nsteps >= 1 && fm[b].nsteps < (1 << 30), "model ", b, ": bad nsteps ", fm[b].nsteps);
+    TORCH_CHECK(std::isfinite(fm[b].lr), "model ", b, ": the learning rate is not finite");
+    S = std::max<int64_t>(S, fm[b].nsteps);
+  }
+  TORCH_CHECK(M * S < (int64_t(1) << 30), "out [", M, ", ", S, ", 2] is too large for one launch");
+  std::vector<char> seen((size_t)M, 0);
+  const int32_t* sc = sched.data_ptr<int32_t>();
+  for (int64_t b = 0; b < M; ++b) {
+    TORCH_CHECK(sc[b] >= 0 && sc[b] < M && !seen[(size_t)sc[b]], "sched is not a permutation of 0 .. ", M - 1);
+    seen[(size_t)sc[b]] = 1;
+  }
+  c10::hip::HIPGuard guard(x.device().index());
+  const at::Tensor models_d = models.to(x.device()), sched_d = sched.to(x.device());
+  // the kernels load no vectors from global memory except the descriptors (32 bytes each)
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(models_d.data_ptr<int64_t>()) % 16 == 0, "descriptors are not 16-byte aligned");
+  auto out = at::zeros({M, S, 2}, flat.options());
+  a.flat = flat.data_ptr<float>();
+  a.m = m.data_ptr<float>();
+  a.v = v.data_ptr<float>();
+  a.iter = iter.data_ptr<int64_t>();
+  a.x = x.data_ptr<float>();
+  a.ldx = x.stride(0);
+  a.y = y.has_value() ? y->data_ptr<float>() : nullptr;
+  a.ldy = y.has_value() ? y->stride(0) : 0;
+  a.order = order.has_value() ? order->data_ptr<int32_t>() : nullptr;
+  a.batch = (int)batch;
+  a.nsteps = (int)S;
+  a.beta1 = (float)beta1;
+  a.beta2 = (float)beta2;
+  a.eps = (float)eps;
+  a.out = out.data_ptr<float>();
+  a.precision = (int)precision;
+  SML_CHECK_HIP(sml::dense_mb_fleet_launch(a, reinterpret_cast<const sml::DenseMBFleetModel*>(models_d.data_ptr<int64_t>()),
+                                           sched_d.data_ptr<int32_t>(), (int)M, stride, cur_stream(x)));
+  return out;
+}
+
 // Fused LSTM Dense head (lstm_head.hip): returns dh = dy . W^T as bf16 [n, 16]; dW / db into grad
 // through map (the dense_wgrad slab layout), this step's [sum sq err, #correct] into acc, out =
 // acc / div, counter + 1.
@@ -1756,6 +1846,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "empty if dense_mb_train can run the table at this batch and precision (0 fp32, 1 bf16), else the reason",
         py::arg("table"), py::arg("batch"), py::arg("nflat") = -1, py::arg("own_targets") = false,
         py::arg("precision") = 0);
+  m.def("dense_mb_train_fleet", &dense_mb_train_fleet,
+        "one launch for M Dense stacks of one architecture, one workgroup per model: flat / m / v [M, stride], iter [M], "
+        "host descriptors models [M, 4] int64 and schedule sched [M] int32 -> [M, max nsteps, 2]",
+        py::arg("flat"), py::arg("m"), py::arg("v"), py::arg("iter"), py::arg("table"), py::arg("x"), py::arg("y"),
+        py::arg("order"), py::arg("models"), py::arg("sched"), py::arg("batch"), py::arg("beta1") = 0.9,
+        py::arg("beta2") = 0.999, py::arg("eps") = 1e-7, py::arg("precision") = 0);
   m.attr("DMB_MAXLAYERS") = (int)sml::DMB_MAXLAYERS;
   m.attr("DMB_MAXW") = (int)sml::DMB_MAXW;
   m.attr("DMB_MAXBATCH") = (int)sml::DMB_MAXBATCH;
