@@ -178,8 +178,24 @@ typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4;
 // (4-way conflict on every ds_write_b64: SQ_LDS_BANK_CONFLICT 3.6-5.9 cycles per LDS instruction
 // in the LSTM backward, profiles/r06); swizzled, the write and the transposed read are both
 // conflict-free, and every lane still reads the same 8 bytes, so the result is bit-identical.
-__device__ __forceinline__ int tr_wr_off(int c, int g) { return c * 32 + 8 * (g ^ ((c >> 2) & 3)); }
-__device__ __forceinline__ int tr_rd_off(int c, int g) { return (4 * g + (c >> 2)) * 32 + 8 * ((c & 3) ^ g); }
+// (the three address helpers are host-callable: tests/test_tr_mask_table.py emulates the read on the CPU)
+__host__ __device__ __forceinline__ int tr_wr_off(int c, int g) { return c * 32 + 8 * (g ^ ((c >> 2) & 3)); }
+__host__ __device__ __forceinline__ int tr_rd_off(int c, int g) { return (4 * g + (c >> 2)) * 32 + 8 * ((c & 3) ^ g); }
+// Lane-masked transposed read.  Result lane c of a 16-lane group receives feature c, and takes it
+// only from the four source lanes with (lane & 3) == c >> 2 (lane 4q+p supplies columns 4p..4p+3).
+// So "the operand with result lanes c >= 8 zeroed" (half 0) is the same read with the source lanes
+// p >= 2 pointed at 8 bytes of zeros, and "c < 8 zeroed" (half 1) the same with p < 2: the mask
+// lives in the loop-invariant address and costs no select.  `cells` is the offset, from the slot,
+// of four 8-byte cells (one per p, so a slot may keep a constant there instead of zeros).
+__host__ __device__ __forceinline__ int tr_rd_off_half(int c, int g, int half, int cells) {
+  const int p = c & 3;
+  return (p >> 1) == half ? tr_rd_off(c, g) : cells + 8 * p;
+}
+// The cell area of three adjacent masked slots: 32 B per slot, 512 B apart like the slots.  Word i
+// of it: zeros, but for the first slot's p == 0 cell, (0, bf16 1.0, 0, 0) -- the half-1 read of
+// that slot keeps feature c == 1 where every row holds the constant 1.0 (a bias input).
+constexpr int TR_MASK_CELL_BYTES = 2 * 512 + 32;
+__host__ __device__ __forceinline__ unsigned tr_mask_cell_word(int i) { return i == 0 ? 0x3F800000u : 0u; }
 __device__ __forceinline__ bf16x4 lds_transpose(bf16x4 v, char* wave_scratch, int c, int g) {
   lds_bf16x4* wr = (lds_bf16x4*)(wave_scratch + tr_wr_off(c, g));
   *wr = v;

@@ -1046,6 +1046,14 @@ __device__ __forceinline__ void tr_write(bf16x4 v, char* slot, int c, int g) {
 __device__ __forceinline__ bf16x4 tr_read(char* slot, int c, int g) {
   return __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_bf16x4*)(slot + tr_rd_off(c, g)));
 }
+// the same read at a lane address the caller keeps (tr_rd_off_half: the lane-masked reads)
+__device__ __forceinline__ bf16x4 tr_read_at(lds_cc* lane_addr) {
+  return __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_bf16x4*)lane_addr);
+}
+// Lane-masked reads (XP 5): the masked slots MASK_SLOT0 .. MASK_SLOT0 + 2 hold xub, h3b, dz2b.  Their
+// cells (tr_mask_cell_word), shared by the workgroup's waves, sit past the rings; the xub slot's
+// constant is the bias feature c == 1 that the second half of dW1's UP operand keeps.
+constexpr int MASK_SLOT0 = 9, MASK_CELL_BYTES = TR_MASK_CELL_BYTES;
 
 // NP packed pairs of whole tiles in ONE interleaved instruction stream (NP = 1 or 2).  Every
 // stage is a loop over the NP pairs, so with NP = 2 the two pairs' dependent MFMA -> activation
@@ -1066,7 +1074,11 @@ __device__ __forceinline__ bf16x4 tr_read(char* slot, int c, int g) {
 // (before d2), dz2b (before d1) -- are written to slots 7..11 as soon as they are packed and read
 // back transposed with the forward ones, the rest of the backward chain hiding the round trip;
 // only dz1b[0..1], produced last, keep the MFMA identity (5 MFMA and 10 cvt_pk fewer per pair, the
-// same bf16 bits).  The LDS-transpose loop spends half its issue
+// same bf16 bits); 5: XP 4 with the lane masks of the MA operands in the read addresses -- xur, h3r
+// and dz2r are each read once through rd_lo and once through rd_hi (tr_rd_off_half: the masked
+// source lanes read cells of zeros) instead of twelve selects per pair, and the pad lane leaves the
+// L1 sum by a multiply; the same bf16 bits again (profiles/r17/mask_reads/SUMMARY.md).
+// The LDS-transpose loop spends half its issue
 // stalls waiting to issue LDS instructions (SQ_WAIT_INST_LDS, profiles/r06/SUMMARY.md §1).
 // RX (tile-packed ring only): the fp32 inputs the loss needs (y - x) are read again from the pair's
 // ring slot at the output layer instead of being held in 9 registers across the whole forward
@@ -1085,7 +1097,8 @@ __device__ __forceinline__ void train_pair_packed(const AEArgs& a, const FragsP&
                                                   const int (&ix)[NP][2], f32x4 acc1[2], f32x4& acc2, f32x4& acc3,
                                                   f32x4 acc4[2], f32x4& acc2b, f32x4& acc4b, float& sq, float& ab,
                                                   float& corr, float& rows, lds_cc* const* xrow = nullptr,
-                                                  lds_cc* const* xupa = nullptr) {
+                                                  lds_cc* const* xupa = nullptr, lds_cc* rd_lo = nullptr,
+                                                  lds_cc* rd_hi = nullptr) {
   // xup: the UP-layout copy of inputs 16 / 17 (lane group g: input 16 + (g & 1) of tile g >> 1)
   static_assert(PACK == PACK_REF && DC == 18, "reference model, D = 18 (outputs 16, 17 packed as UP)");
   static_assert(NP == 1 || NP == 2, "one or two pairs per iteration");
@@ -1093,9 +1106,17 @@ __device__ __forceinline__ void train_pair_packed(const AEArgs& a, const FragsP&
   const bf16x4 zb = {0, 0, 0, 0};
   const bool pad_lane = (g == 3);
   const bool lo = c < 8;   // lanes holding tile 0's half of a packed operand (as n or m = c)
+  const float pad_m = pad_lane ? 0.f : 1.f;
   auto stand_in = [](int p, int u) { return TP && p == NP - 1 && u == 1; };
   constexpr bool EW = XP == 1 || XP >= 3, MA = XP >= 1, TRM = XP == 2;
-  constexpr bool EB = XP == 4;   // the early backward writes (slots 7..11)
+  constexpr bool EB = XP >= 4;   // the early backward writes (slots 7..11)
+  constexpr bool MR = XP == 5;   // lane masks by masked transposed reads, pad lane by a multiply
+  // transpose slots.  MR renumbers them so that the three lane-masked operands (xub, h3b, dz2b) are
+  // adjacent: their zero cells (tr_mask_cell_word) then span two slot strides and 32 bytes.
+  constexpr int S_XU = MR ? 9 : 2, S_H1 = MR ? 2 : 3, S_H2 = MR ? 4 : 5, S_H3 = MR ? 10 : 6, S_DZ4 = MR ? 5 : 7,
+                S_DZ4U = MR ? 7 : 9, S_DZ3 = MR ? 8 : 10, S_DZ2 = 11;
+  static_assert(!MR || (NP == 1 && S_XU == MASK_SLOT0 && S_H3 == MASK_SLOT0 + 1 && S_DZ2 == MASK_SLOT0 + 2),
+                "masked reads: one pair per wave, the masked slots where the kernel put their cells");
   // identity B operand (lane (n = c, g) holds k = 4g..4g+3): 1 where k == n
   bf16x4 ident;
 #pragma unroll
@@ -1114,7 +1135,7 @@ __device__ __forceinline__ void train_pair_packed(const AEArgs& a, const FragsP&
     if constexpr (EW) {   // slots 0..6 of the pair: the forward operands of the weight gradients
       tr_write(xb0[p][0], scr + (p * TS + 0) * 512, c, g);
       tr_write(xb0[p][1], scr + (p * TS + 1) * 512, c, g);
-      tr_write(xub[p], scr + (p * TS + 2) * 512, c, g);
+      tr_write(xub[p], scr + (p * TS + S_XU) * 512, c, g);
     }
   }
 #pragma unroll
@@ -1143,7 +1164,7 @@ __device__ __forceinline__ void train_pair_packed(const AEArgs& a, const FragsP&
 #pragma unroll
       for (int i = 0; i < 4; ++i) h1[p][u][i] = tanh_exp2(z1[p][u][i]);
       h1b[p][u] = pack4(h1[p][u]);
-      if constexpr (EW) tr_write(h1b[p][u], scr + (p * TS + 3 + u) * 512, c, g);
+      if constexpr (EW) tr_write(h1b[p][u], scr + (p * TS + S_H1 + u) * 512, c, g);
     }
   // Keras L1 activity-regulariser gradient l1 * sign(h1) as one v_med3 (see train_tile), computed
   // off the critical path and fed to the dh1 MFMA as its accumulator input (EW: right before it,
@@ -1166,7 +1187,7 @@ __device__ __forceinline__ void train_pair_packed(const AEArgs& a, const FragsP&
 #pragma unroll
     for (int i = 0; i < 4; ++i) h2[p][i] = relu_fast(z2[p][i]);
     h2b[p] = pack4(h2[p]);
-    if constexpr (EW) tr_write(h2b[p], scr + (p * TS + 5) * 512, c, g);
+    if constexpr (EW) tr_write(h2b[p], scr + (p * TS + S_H2) * 512, c, g);
   }
 #pragma unroll
   for (int p = 0; p < NP; ++p) z3[p] = mfma16(F.w3t, h2b[p], zero4);
@@ -1175,7 +1196,7 @@ __device__ __forceinline__ void train_pair_packed(const AEArgs& a, const FragsP&
 #pragma unroll
     for (int i = 0; i < 4; ++i) h3[p][i] = tanh_exp2(z3[p][i]);
     h3b[p] = pack4(h3[p]);
-    if constexpr (EW) tr_write(h3b[p], scr + (p * TS + 6) * 512, c, g);
+    if constexpr (EW) tr_write(h3b[p], scr + (p * TS + S_H3) * 512, c, g);
   }
   // output layer: outputs 0..15 per tile, outputs 16 / 17 of BOTH tiles in one register (UP:
   // lane group g = output 16 + (g & 1) of tile g >> 1; w4u's rows m = 4q, so only C entry 0 is used)
@@ -1245,9 +1266,9 @@ __device__ __forceinline__ void train_pair_packed(const AEArgs& a, const FragsP&
     for (int u = 0; u < 2; ++u) dz4b[p][u] = pack4(dz4[p][u]);
     dz4bu[p] = pack4(f32x4{dz4up[p], 0.f, 0.f, 0.f});
     if constexpr (EB) {
-      tr_write(dz4b[p][0], scr + (p * TS + 7) * 512, c, g);
-      tr_write(dz4b[p][1], scr + (p * TS + 8) * 512, c, g);
-      tr_write(dz4bu[p], scr + (p * TS + 9) * 512, c, g);
+      tr_write(dz4b[p][0], scr + (p * TS + S_DZ4) * 512, c, g);
+      tr_write(dz4b[p][1], scr + (p * TS + S_DZ4 + 1) * 512, c, g);
+      tr_write(dz4bu[p], scr + (p * TS + S_DZ4U) * 512, c, g);
     }
   }
 #pragma unroll
@@ -1261,7 +1282,7 @@ __device__ __forceinline__ void train_pair_packed(const AEArgs& a, const FragsP&
 #pragma unroll
     for (int i = 0; i < 4; ++i) dz3[i] = d3[p][i] * fmaf(-h3[p][i], h3[p][i], 1.0f);   // 0 at the bias slots (h = 1)
     dz3b[p] = pack4(dz3);
-    if constexpr (EB) tr_write(dz3b[p], scr + (p * TS + 10) * 512, c, g);
+    if constexpr (EB) tr_write(dz3b[p], scr + (p * TS + S_DZ3) * 512, c, g);
   }
 #pragma unroll
   for (int p = 0; p < NP; ++p) d2[p] = mfma16(F.w3b, dz3b[p], zero4);
@@ -1271,7 +1292,7 @@ __device__ __forceinline__ void train_pair_packed(const AEArgs& a, const FragsP&
 #pragma unroll
     for (int i = 0; i < 4; ++i) dz2[i] = h2[p][i] > 0.f ? d2[p][i] : 0.f;
     dz2b[p] = pack4(dz2);
-    if constexpr (EB) tr_write(dz2b[p], scr + (p * TS + 11) * 512, c, g);
+    if constexpr (EB) tr_write(dz2b[p], scr + (p * TS + S_DZ2) * 512, c, g);
   }
   f32x4 d1[NP][2];
   if constexpr (MA) l1_sign();
@@ -1291,7 +1312,12 @@ __device__ __forceinline__ void train_pair_packed(const AEArgs& a, const FragsP&
           dz1[i] = 0.f;
           continue;
         }
-        ab += (i == 3 && pad_lane) ? 0.f : fabsf(hv);
+        // MR: the pad lane's slot 3 leaves the L1 sum by a multiply with the lane-invariant 0 / 1
+        // (|h| * 1 and ab + 0 are exact: the same bits as the select, one VALU less)
+        if (MR && i == 3)
+          ab = fmaf(fabsf(hv), pad_m, ab);
+        else
+          ab += (i == 3 && pad_lane) ? 0.f : fabsf(hv);
         dz1[i] = d1[p][u][i] * fmaf(-hv, hv, 1.0f);
       }
       dz1b[p][u] = pack4(dz1);
@@ -1310,7 +1336,29 @@ __device__ __forceinline__ void train_pair_packed(const AEArgs& a, const FragsP&
   for (int p = 0; p < NP; ++p) {
     char* sp = scr + p * TS * 512;
     bf16x4 xr0[2], dz1r[2], h1r[2], dz4r[2], xur, dz4ru, dz2r, h2r, dz3r, h3r;
-    if constexpr (EB) {
+    bf16x4 xur_m[2], dz2r_m[2], h3r_m[2];   // MR: the [c < 8 | c >= 8] lane-masked copies, as read
+    if constexpr (MR) {
+      // the order of XP 4; each masked operand once through rd_lo (result lanes c >= 8 are zeros)
+      // and once through rd_hi (c < 8 zeros; the xub slot's cell keeps the bias feature c == 1)
+      h3r = tr_read(sp + S_H3 * 512, c, g);
+      h3r_m[0] = tr_read_at(rd_lo + S_H3 * 512);
+      h3r_m[1] = tr_read_at(rd_hi + S_H3 * 512);
+      dz4r[0] = tr_read(sp + S_DZ4 * 512, c, g);
+      dz4r[1] = tr_read(sp + (S_DZ4 + 1) * 512, c, g);
+      dz4ru = tr_read(sp + S_DZ4U * 512, c, g);
+      h2r = tr_read(sp + S_H2 * 512, c, g);
+      dz3r = tr_read(sp + S_DZ3 * 512, c, g);
+      h1r[0] = tr_read(sp + S_H1 * 512, c, g);
+      h1r[1] = tr_read(sp + (S_H1 + 1) * 512, c, g);
+      dz2r_m[0] = tr_read_at(rd_lo + S_DZ2 * 512);
+      dz2r_m[1] = tr_read_at(rd_hi + S_DZ2 * 512);
+      xr0[0] = tr_read(sp + 0 * 512, c, g);
+      xr0[1] = tr_read(sp + 1 * 512, c, g);
+      xur_m[0] = tr_read_at(rd_lo + S_XU * 512);
+      xur_m[1] = tr_read_at(rd_hi + S_XU * 512);
+      dz1r[0] = mfma_tr(dz1b[p][0]);
+      dz1r[1] = mfma_tr(dz1b[p][1]);
+    } else if constexpr (EB) {
       // LDS reads return in order (behind the RX re-read of the ring slot), so the operands of
       // the gradient MFMAs that can go first are asked for first: dW4, dW3, dW2 need nothing
       // else; dW1's partners dz1r come off the matrix pipe last, so xr0 / xur are read last.
@@ -1385,11 +1433,18 @@ __device__ __forceinline__ void train_pair_packed(const AEArgs& a, const FragsP&
     }
     acc1[0] = mfma32(xr0[0], xr0[1], dz1r[0], dz1r[1], acc1[0]);
     // rows 16 + m: m = 0 / 4 tile 0's inputs 16 / 17, m = 8 / 12 tile 1's, m = 1 the bias (both)
-    acc1[1] = mfma32(lo ? xur : zb, (!lo || c == 1) ? xur : zb, dz1r[0], dz1r[1], acc1[1]);
+    if constexpr (MR)
+      acc1[1] = mfma32(xur_m[0], xur_m[1], dz1r[0], dz1r[1], acc1[1]);
+    else
+      acc1[1] = mfma32(lo ? xur : zb, (!lo || c == 1) ? xur : zb, dz1r[0], dz1r[1], acc1[1]);
     // dW2 / dW4 (outputs 0..15): each tile against the whole packed operand, in an accumulator
     // of its own (only its half -- n < 8 / m < 8 for tile 0 -- is kept when the slab is written):
     // two 16x16x16 instead of a 16x16x32 on lane-masked copies (no per-pair selects)
-    if constexpr (MA) {
+    if constexpr (MR) {   // MA with the masks already in the operands
+      acc2 = mfma32(h1r[0], h1r[1], dz2r_m[0], dz2r_m[1], acc2);
+      acc3 = mfma16(h2r, dz3r, acc3);
+      acc4[0] = mfma32(h3r_m[0], h3r_m[1], dz4r[0], dz4r[1], acc4[0]);
+    } else if constexpr (MA) {
       // 8 fewer accumulator registers: each tile's contraction against its own half of the packed
       // operand (the other half lane-masked to 0) in ONE 16x16x32 -- dW2 columns n < 8 / n >= 8
       // (lane c) from tile 0 / 1, dW4 rows m < 8 / m >= 8 (lane c of the A operand) likewise; the
@@ -1435,13 +1490,16 @@ constexpr int ring_bytes_pf() { return ILP == 3 ? PF * (CM ? 912 : 1168) : ring_
 // on the compact one.  XP 4 (TS 12, the early backward writes) is built for the compact ring only:
 // 39 424 B there; the 18-column and the raw-row 4-wave instances are at 39 424 B with TS 10 already
 // and would drop to three workgroups per CU, so they keep XP 3.
-template <int PF, int OCC, int ILP, int TS, int NPW = 1, int CM = 0>
+// MC: bytes of lane-mask cells past the rings (XP 5: 40 480 B, inside the 40 960 B that four
+// workgroups per CU allow).
+template <int PF, int OCC, int ILP, int TS, int NPW = 1, int CM = 0, int MC = 0>
 struct AELds {
   static constexpr int SCR = (ILP == 3 ? NPW * TS : 10) * 512;      // per wave (0: MFMA transposes)
   static constexpr int NORM_OFF = ILP == 3 ? WAVES * SCR : SLAB_BYTES;
   static constexpr int RING_OFF = NORM_OFF + NORM_BYTES;
   static constexpr int RING = ring_bytes_pf<OCC, ILP, PF, CM>();
-  static constexpr int END = RING_OFF + (PF > 0 ? WAVES * RING : 0);
+  static constexpr int CELLS_OFF = RING_OFF + (PF > 0 ? WAVES * RING : 0);
+  static constexpr int END = CELLS_OFF + MC;
   static constexpr int BYTES = END > SLAB_BYTES ? END : SLAB_BYTES;
 };
 
@@ -1456,7 +1514,10 @@ __global__ __launch_bounds__(WAVES * 64, OCC) void ae_train_kernel(AEArgs a) {
   constexpr bool CMP = CM != 0;
   static_assert(!CMP || (ILP == 3 && XM == 1 && DC == 18), "compact ring: packed pairs, tile-packed ring, D = 18");
   constexpr int DR = CMP ? 14 : DC;   // floats per ring row (0: a.D)
-  using L = AELds<PF, OCC, ILP, (XP == 2 ? 0 : TS), NPW, CM>;
+  constexpr bool MR = XP == 5;   // lane masks by masked transposed reads (train_pair_packed)
+  static_assert(!MR || (ILP == 3 && XM == 1 && NPW == 1 && PF == 4 && TS == 12), "XP 5: the unrolled two-slot pair loop");
+  using L = AELds<PF, OCC, ILP, (XP == 2 ? 0 : TS), NPW, CM, MR ? MASK_CELL_BYTES : 0>;
+  static_assert(L::BYTES <= 40960 || OCC < 4, "four workgroups per CU");
   static_assert(NPW == 1 || ILP == 3, "several pairs per iteration: packed pairs only");
   constexpr int RING = L::RING;
   static_assert(WAVES * (ILP == 3 && NPW == 1 ? TS : 10) * 512 <= SLAB_BYTES,
@@ -1495,6 +1556,10 @@ __global__ __launch_bounds__(WAVES * 64, OCC) void ae_train_kernel(AEArgs a) {
   else
     load_frags<FAST, FAST && prescaled_tanh<PACK>(), FAST && inject_bias_slots<PACK>()>(a, c, g, F, true);
   const float pad1 = (g == 3) ? 1.0f : 0.0f;
+  if constexpr (MR) {   // the lane-mask cells: zeros, and bf16 1.0 at feature 1 of the xub slot's first cell
+    for (int i = threadIdx.x; i < MASK_CELL_BYTES / 4; i += WAVES * 64)
+      smem[L::CELLS_OFF / 4 + i] = __uint_as_float(tr_mask_cell_word(i));
+  }
   __syncthreads();  // normaliser visible (before any LDS-DMA is in flight)
 
   f32x4 acc1[2], acc2, acc3, acc4[2], acc2b, acc4b;   // acc2b / acc4b: packed pairs' tile-1 halves
@@ -1656,6 +1721,15 @@ __global__ __launch_bounds__(WAVES * 64, OCC) void ae_train_kernel(AEArgs a) {
             lds_cc* axb = (lds_cc*)(ring + (slotb - 16) + c);   // XM 1: the tile's argmax byte of row c
             asm volatile("" : "+v"(rowb), "+v"(upb));
             asm volatile("" : "+v"(axb));
+            // MR: the lane's two masked transposed-read addresses (tr_rd_off_half), one register each
+            lds_cc* rd_lo = nullptr;
+            lds_cc* rd_hi = nullptr;
+            if constexpr (MR) {
+              const int cells = L::CELLS_OFF - MASK_SLOT0 * 512 - wid * L::SCR;   // from this wave's slot
+              rd_lo = (lds_cc*)scr + tr_rd_off_half(c, g, 0, cells);
+              rd_hi = (lds_cc*)scr + tr_rd_off_half(c, g, 1, cells);
+              asm volatile("" : "+v"(rd_lo), "+v"(rd_hi));
+            }
             auto trip = [&](auto slot) {
               constexpr int rs = decltype(slot)::value, ws = (rs + PS - 1) % PS;
               issue_next(ws);
@@ -1676,7 +1750,8 @@ __global__ __launch_bounds__(WAVES * 64, OCC) void ae_train_kernel(AEArgs a) {
               xup[0] = *(lds_f*)xu[0];
               constexpr bool RX = OCC >= 4;
               train_pair_packed<PACK, DC, false, TS, 1, XP, RX, CMP, true, false>(
-                  a, FP, scr, c, g, xf, xup, ix, acc1, acc2, acc3, acc4, acc2b, acc4b, sq, ab, corr, rows, xr, xu);
+                  a, FP, scr, c, g, xf, xup, ix, acc1, acc2, acc3, acc4, acc2b, acc4b, sq, ab, corr, rows, xr, xu, rd_lo,
+                  rd_hi);
             };
             // one copy of each slot's trip: the wave leaves the unrolled body after its last trip
             for (unsigned k = ntrip; k > 0; k -= PS) {
@@ -1841,21 +1916,30 @@ __global__ __launch_bounds__(WAVES * 64, OCC) void ae_train_kernel(AEArgs a) {
   // per-wave slab in LDS (every slot written exactly once per wave)
   __syncthreads();  // all waves done with their transpose scratch
   float* my = smem + wid * NSLOT;
+  // MR: the slab indices are derived again from the lane id here (opaque to the compiler), so that
+  // they are not carried in registers across the pair loop, which has none to spare
+  int ce = c, ge = g;
+  if constexpr (MR) {
+    int le = threadIdx.x & 63;
+    asm volatile("" : "+v"(le));
+    ce = le & 15;
+    ge = le >> 4;
+  }
   if constexpr (ILP == 3) {   // tile 1's halves: dW2 columns n >= 8, dW4 rows m >= 8 (lane groups 2, 3)
     if constexpr (XP == 0) {   // XP >= 1 (MA) holds both halves in acc2 / acc4[0]
-      acc2 = c < 8 ? acc2 : acc2b;
-      acc4[0] = g < 2 ? acc4[0] : acc4b;
+      acc2 = ce < 8 ? acc2 : acc2b;
+      acc4[0] = ge < 2 ? acc4[0] : acc4b;
     }
   }
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
-    const int m = 4 * g + i;
-    my[OFF1 + m * 16 + c] = acc1[0][i];
-    my[OFF1 + (16 + m) * 16 + c] = acc1[1][i];
-    my[OFF2 + m * 16 + c] = acc2[i];
-    my[OFF3 + m * 16 + c] = acc3[i];
-    my[OFF4 + m * 32 + c] = acc4[0][i] * (2.0f / (float)a.D);
-    my[OFF4 + m * 32 + 16 + c] = acc4[1][i] * (2.0f / (float)a.D);
+    const int m = 4 * ge + i;
+    my[OFF1 + m * 16 + ce] = acc1[0][i];
+    my[OFF1 + (16 + m) * 16 + ce] = acc1[1][i];
+    my[OFF2 + m * 16 + ce] = acc2[i];
+    my[OFF3 + m * 16 + ce] = acc3[i];
+    my[OFF4 + m * 32 + ce] = acc4[0][i] * (2.0f / (float)a.D);
+    my[OFF4 + m * 32 + 16 + ce] = acc4[1][i] * (2.0f / (float)a.D);
   }
   sq = wave_sum(sq);
   ab = wave_sum(ab);
@@ -2236,15 +2320,18 @@ static int pair_occ() {
   const char* e = getenv("SML_AE_PAIR_OCC");
   return (e && (e[0] == '2' || e[0] == '3' || e[0] == '4')) ? e[0] - '0' : 4;
 }
-// SML_AE_PAIR_XP=0|1|2|3|4: the packed-pair weight-gradient operand path (train_pair_packed's XP);
+// SML_AE_PAIR_XP=0|1|2|3|4|5: the packed-pair weight-gradient operand path (train_pair_packed's XP);
 // at SML_AE_PAIR_OCC=4, 0 means 1 (the 4-wave build needs the early writes' registers).  4 (the
-// early backward writes, TS 12) is built for the compact ring at 4 waves only and means 3
-// everywhere else.  Default 4: 56.78-57.60 vs 55.62-55.67 G rows/s for XP 3 (the parent build) in
-// alternating runs, bit-identical results; SQ_WAIT_INST_LDS rises from 61 to 232 cycles per trip
-// and the wave still spends 183 cycles fewer in a trip (profiles/r10/early_bwd/SUMMARY.md).
+// early backward writes, TS 12) and 5 (4 with the lane masks in the read addresses) are built for
+// the compact ring at 4 waves only and mean 3 everywhere else.  XP 4 over XP 3: 56.78-57.60 vs
+// 55.62-55.67 G rows/s in alternating runs (profiles/r10/early_bwd/SUMMARY.md).  Default 5:
+// 54.98-55.28 vs 54.38-54.56 G rows/s for XP 4 (the parent build) in alternating runs, and 57.00-57.28
+// vs 56.24-56.53 on another box, bit-identical results; 14 VALU fewer and 4 LDS reads more per trip,
+// SQ_WAIT_INST_LDS rises from 232 to 300 cycles per trip and the wave still spends 88 cycles fewer
+// in a trip (profiles/r17/mask_reads/SUMMARY.md).
 static int pair_xp() {
   const char* e = getenv("SML_AE_PAIR_XP");
-  return (e && e[0] >= '0' && e[0] <= '4') ? e[0] - '0' : 4;
+  return (e && e[0] >= '0' && e[0] <= '5') ? e[0] - '0' : 5;
 }
 static int train_occupancy() {
   const char* e = getenv("SML_AE_OCC");
@@ -2271,7 +2358,7 @@ int ae_waves_per_block() { return WAVES; }
 
 // What the calling thread's last ae_train_launch ran, for tests that A/B two instances in one
 // process: the XP and TS of the 4-wave compact-ring packed-pair instances (-1 for every other
-// variant) and the launched instance's static LDS size as the runtime reports it.
+// variant; XP 3, 4 or 5) and the launched instance's static LDS size as the runtime reports it.
 struct LastVariant {
   const void* fn = nullptr;
   int xp = -1, ts = -1;
@@ -2375,6 +2462,8 @@ hipError_t ae_train_launch(const float* x, int64_t n, int64_t ld, const float* s
       if (cm) {   // the compact-ring twin of every variant below, and the XP 4 instance
         if (po == 2)
           hipLaunchKernelGGL((ae_train_kernel<PACK_REF, true, 8, 2, 18, 1, 3, 10, 2, 0, 1>), gd, bd, 0, stream, a);
+        else if (po == 4 && xp == 5)   // XP 4 with the lane masks in the read addresses: 40 480 B
+          launch_noted(ae_train_kernel<PACK_REF, true, 4, 4, 18, 1, 3, 12, 1, 5, 1>, 5, 12);
         else if (po == 4 && xp == 4)   // TS 12: 39 424 B, still four workgroups per CU
           launch_noted(ae_train_kernel<PACK_REF, true, 4, 4, 18, 1, 3, 12, 1, 4, 1>, 4, 12);
         else if (po == 4 && xp >= 2)
