@@ -7,7 +7,7 @@ namespace sml {
 
 // ---- dense autoencoder (ae_fused.hip) ----
 int ae_nslot();
-int ae_train_blocks_per_cu();  // most resident 256-thread workgroups per CU of any train variant (4)
+int ae_train_blocks_per_cu();  // 8: the host sizes its partials buffer for 2 x this many workgroups per CU
 int ae_nparam();
 int ae_waves_per_block();
 int ae_train_grid(int64_t n, int max_blocks);

@@ -45,6 +45,7 @@
 
 #include "sml_common.h"
 #include "sml_adam.h"
+#include "sml_ae_variants.h"
 
 using namespace sml;
 
@@ -84,8 +85,8 @@ struct AEArgs {
 
 // Activation codes are compile-time when PACK >= 0 (a1 | a2<<2 | a3<<4 | a4<<6),
 // runtime otherwise.  The reference model (tanh, relu, tanh, relu) is PACK 0x66.
-constexpr int PACK_REF = ACT_TANH | (ACT_RELU << 2) | (ACT_TANH << 4) | (ACT_RELU << 6);
-constexpr int PACK_DYN = -1;
+// (PACK_REF, PACK_DYN: sml_ae_variants.h)
+static_assert(PACK_REF == (ACT_TANH | (ACT_RELU << 2) | (ACT_TANH << 4) | (ACT_RELU << 6)), "the reference pack");
 
 template <int PACK>
 __device__ __forceinline__ int act_of(const AEArgs& a, int i) {
@@ -855,7 +856,6 @@ __device__ __forceinline__ void train_tiles_ilp(const AEArgs& a, const Frags& F,
 // weight, this one a finite input by zero: both products are 0), its dW1 row is written as the
 // exact 0 it is (packed_fold_src), and the loss selects 0 as its target.  Everything else is
 // the same instruction on the same operands, so the results are the 18-column loop's.
-constexpr unsigned kLiveCardata = 0x3FFFFu & ~((1u << 0) | (1u << 2) | (1u << 4) | (1u << 5));
 __host__ __device__ constexpr bool cm_dead(int f) { return f == 0 || f == 2 || f == 4 || f == 5; }
 // byte offset, from the row's first compact float, of the lane's four floats: {0, 8, 24, 40} for
 // g = 0..3.  Branch-free on purpose: a nested ?: over g became exec-masked branches inside the loop.
@@ -1061,9 +1061,6 @@ constexpr int MASK_SLOT0 = 9, MASK_CELL_BYTES = TR_MASK_CELL_BYTES;
 // VALU issues while the other's MFMA result is in flight (the chain has ~13 dependent stages;
 // one pair per wave leaves most of a trip waiting on them, profiles/r06/SUMMARY.md §1).  The
 // pairs share the weight fragments and the gradient accumulators; each has TS transpose slots.
-// TP: the LAST pair's second tile is a stand-in whose loss, metrics and gradients are all masked
-// to zero (kept for an odd last tile; the kernel's contiguous-pair loop takes even tile counts
-// only and instantiates TP = false).
 // XP: how the weight-gradient operands reach the rows-on-K layout.  0: LDS transposes at the end
 // of the step; 1: the forward ones written to LDS as soon as they exist (EW), the tile halves of
 // dW2 / dW4 in one accumulator each (MA); 2: no LDS at all -- each operand is the A operand of one
@@ -1090,7 +1087,7 @@ constexpr int MASK_SLOT0 = 9, MASK_CELL_BYTES = TR_MASK_CELL_BYTES;
 // WA: the variant is only ever launched with want_acc (the tile-packed ring variants, XM 1), so the
 // metric block is unconditional: no branch, and the argmax of y fills the backward chain's MFMA waits.
 // RC: count the rows here (false: the caller sets them from its trip count after the loop).
-template <int PACK, int DC, bool TP, int TS = 10, int NP = 1, int XP = 0, bool RX = false, bool CM = false,
+template <int PACK, int DC, int TS = 10, int NP = 1, int XP = 0, bool RX = false, bool CM = false,
           bool WA = false, bool RC = true>
 __device__ __forceinline__ void train_pair_packed(const AEArgs& a, const FragsP& F, char* scr, int c, int g,
                                                   const f32x4 (&xf)[NP][2][2], const float (&xup)[NP],
@@ -1107,7 +1104,6 @@ __device__ __forceinline__ void train_pair_packed(const AEArgs& a, const FragsP&
   const bool pad_lane = (g == 3);
   const bool lo = c < 8;   // lanes holding tile 0's half of a packed operand (as n or m = c)
   const float pad_m = pad_lane ? 0.f : 1.f;
-  auto stand_in = [](int p, int u) { return TP && p == NP - 1 && u == 1; };
   constexpr bool EW = XP == 1 || XP >= 3, MA = XP >= 1, TRM = XP == 2;
   constexpr bool EB = XP >= 4;   // the early backward writes (slots 7..11)
   constexpr bool MR = XP == 5;   // lane masks by masked transposed reads, pad lane by a multiply
@@ -1175,7 +1171,7 @@ __device__ __forceinline__ void train_pair_packed(const AEArgs& a, const FragsP&
 #pragma unroll
       for (int u = 0; u < 2; ++u)
 #pragma unroll
-        for (int i = 0; i < 4; ++i) l1s[p][u][i] = stand_in(p, u) ? 0.f : __builtin_amdgcn_fmed3f(h1[p][u][i], -a.l1, a.l1);
+        for (int i = 0; i < 4; ++i) l1s[p][u][i] = __builtin_amdgcn_fmed3f(h1[p][u][i], -a.l1, a.l1);
   };
   if constexpr (!MA) l1_sign();
   f32x4 z2[NP], h2[NP], h3[NP], z3[NP];
@@ -1237,13 +1233,11 @@ __device__ __forceinline__ void train_pair_packed(const AEArgs& a, const FragsP&
       for (int i = 0; i < 4; ++i) {
         y[p][u][i] = relu_fast(z4[p][u][i]);
         float e = (CM && i < 3) ? fmaf(-xl[p][u][i], cm_m[i], y[p][u][i]) : y[p][u][i] - xl[p][u][i];
-        if (stand_in(p, u)) e = 0.f;
         sq = fmaf(e, e, sq);
         dz4[p][u][i] = y[p][u][i] > 0.f ? e : 0.f;   // relu'; x 2/D folded into F.w4b / the acc4 slab
       }
     yup[p] = relu_fast(z4u[p][0]);
     float eup = yup[p] - xul[p];
-    if (TP && p == NP - 1) eup = g < 2 ? eup : 0.f;
     sq = fmaf(eup, eup, sq);
     dz4up[p] = yup[p] > 0.f ? eup : 0.f;
   }
@@ -1253,10 +1247,10 @@ __device__ __forceinline__ void train_pair_packed(const AEArgs& a, const FragsP&
       const int iy = row_argmax_up_pair(y[p][0], y[p][1], yup[p], g);
       const int sel = -(g & 1);   // bit-select: a ?: on the pair becomes a scratch array indexed by g
       const int ixs = (ix[p][0] & ~sel) | (ix[p][1] & sel);
-      corr += (((TP && p == NP - 1) ? g == 0 : g < 2) && iy == ixs) ? 1.f : 0.f;
+      corr += (g < 2 && iy == ixs) ? 1.f : 0.f;
     }
   }
-  if constexpr (RC) rows += (g == 0) ? (TP ? 2.f * NP - 1.f : 2.f * NP) : 0.f;
+  if constexpr (RC) rows += (g == 0) ? 2.f * NP : 0.f;
 
   bf16x4 dz4b[NP][2], dz1b[NP][2], dz4bu[NP], dz3b[NP], dz2b[NP];
   f32x4 d3[NP], d2[NP];
@@ -1308,10 +1302,6 @@ __device__ __forceinline__ void train_pair_packed(const AEArgs& a, const FragsP&
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         const float hv = h1[p][u][i];
-        if (stand_in(p, u)) {
-          dz1[i] = 0.f;
-          continue;
-        }
         // MR: the pad lane's slot 3 leaves the L1 sum by a multiply with the lane-invariant 0 / 1
         // (|h| * 1 and ab + 0 are exact: the same bits as the select, one VALU less)
         if (MR && i == 3)
@@ -1481,6 +1471,7 @@ constexpr int ring_bytes() { return ILP == 3 ? (OCC >= 4 ? 4672 : 7008) : OCC >=
 // compact ring (CM): 64 * 14 + 16 = 912 B per tile
 template <int OCC, int ILP, int PF, int CM = 0>
 constexpr int ring_bytes_pf() { return ILP == 3 ? PF * (CM ? 912 : 1168) : ring_bytes<OCC, ILP>(); }
+static_assert(ring_bytes<4>() == kRing1Tile4w && ring_bytes<3>() == kRing1Tile3w, "the launcher's ring depths");
 
 // LDS layout.  Default: [slab area = per-wave transpose scratch (10 x 512 B) | normaliser | rings].
 // Packed pairs (ILP 3): [TS x 512 B transpose scratch per wave | normaliser | rings], and the
@@ -1507,9 +1498,12 @@ struct AELds {
 // XP (packed pairs only): the weight-gradient operand path of train_pair_packed.
 // CM (packed pairs on the tile-packed ring only): the compact ring of the 14 live cardata
 // features: 912-B tile slots, a pair = two DMAs of 1024 + 800 B.
-template <int PACK, bool VEC, int PF, int OCC, int DC = 0, int XM = 0, int ILP = 1, int TS = 10, int NPW = 1,
-          int XP = 0, int CM = 0>
-__global__ __launch_bounds__(WAVES * 64, OCC) void ae_train_kernel(AEArgs a) {
+// V: the instance's eleven values as a named type (the variants of sml_ae_variants.h).
+template <class V>
+__global__ __launch_bounds__(WAVES * 64, V::OCC) void ae_train_kernel(AEArgs a) {
+  constexpr int PACK = V::PACK, PF = V::PF, OCC = V::OCC, DC = V::DC, XM = V::XM, ILP = V::ILP, TS = V::TS,
+                NPW = V::NPW, XP = V::XP, CM = V::CM;
+  constexpr bool VEC = V::VEC;
   constexpr bool FAST = zero_preserving<PACK>();
   constexpr bool CMP = CM != 0;
   static_assert(!CMP || (ILP == 3 && XM == 1 && DC == 18), "compact ring: packed pairs, tile-packed ring, D = 18");
@@ -1525,10 +1519,9 @@ __global__ __launch_bounds__(WAVES * 64, OCC) void ae_train_kernel(AEArgs a) {
   static_assert(ILP == 3 || TS == 10, "shared transpose slots: packed pairs only");
   static_assert(PF == 0 || CMP || PF * 64 * 17 <= RING, "ring slots must fit the smallest ring tile");
   // XM: x-argmax mode. 0 in-kernel argmax; 1 tile-packed ring (rows + ingest-time argmax
-  // bytes per tile, pack_tiles_argmax); 2 / 3 A/B probes that skip the argmax of x entirely (wrong accuracy, timing
-  // only: 2 with the plain tile order, 3 with the chunked order) -- they separate the VALU
-  // saving from the cost of delivering the bytes (profiles/r02/SUMMARY.md)
-  constexpr bool XA = XM != 0;
+  // bytes per tile, pack_tiles_argmax)
+  static_assert(XM == 0 || XM == 1, "x-argmax mode");
+  constexpr bool XA = XM == 1;
   static_assert(XM != 1 || (DC > 0 && PF > 0 && PF * (64 * DR + 16) <= RING), "XA: compile-time D, ring slots + argmax");
   // one LDS array: per-wave transpose scratch during the tile loop, per-wave
   // gradient slabs afterwards | the normaliser | (PF > 0) the per-wave input rings
@@ -1597,22 +1590,16 @@ __global__ __launch_bounds__(WAVES * 64, OCC) void ae_train_kernel(AEArgs a) {
         glds16(src, voff, dst);
         if (lane < nl2) glds16(src + 1024, voff, dst + 1024);
       };
-      // Tile order of this wave: chunks of CH consecutive tiles, chunks interleaved over
-      // the waves (CH = 1: plain interleave; CH = 8 only in the XM 3 timing probe).
-      constexpr int CH = XM == 3 ? 8 : 1;
-      // next tile in this wave's order (CH = 1: + stride; else +1 inside a chunk, then
-      // on to the wave's next chunk); increasing, so t >= nfull ends the wave
-      auto next_tile = [&](int64_t t) -> int64_t {
-        if constexpr (CH == 1) return t + stride;
-        return ((t + 1) & (CH - 1)) ? t + 1 : t + 1 + (stride - 1) * CH;
-      };
-      const int64_t t0 = ufirst * CH;
+      // Tile order of this wave: the tiles are interleaved over the waves;
+      // increasing, so t >= nfull ends the wave.  (A lambda on purpose: with `+ stride` written
+      // out at its three uses, four of the one-tile ring instances are scheduled differently.)
+      auto next_tile = [&](int64_t t) -> int64_t { return t + stride; };
+      const int64_t t0 = ufirst;
       if constexpr (ILP >= 2) {
         // ILP 2: tile pairs (t, t + stride), two issues per iteration, the pair's two tiles
         // landed = vmcnt(NV * (PF - 2)); a last unpaired tile runs alone (U = 1).  ILP 3:
         // contiguous tile pairs (below).
-        static_assert((XM == 1 || (XM == 0 && ILP == 3)) && CH == 1 && PF >= 3,
-                      "tile pairs: tile-packed ring (or raw rows, packed pairs), plain order");
+        static_assert((XM == 1 || ILP == 3) && PF >= 3, "tile pairs: tile-packed ring (or raw rows, packed pairs)");
         auto ring_tile = [&](int slot, f32x4 xf[2], int& ix) {
           typedef __attribute__((address_space(3))) const unsigned char lds_u8;
           if constexpr (XM == 1) ix = (int)*(lds_u8*)(ring + slot * slotb + (slotb - 16) + c);
@@ -1749,7 +1736,7 @@ __global__ __launch_bounds__(WAVES * 64, OCC) void ae_train_kernel(AEArgs a) {
               }
               xup[0] = *(lds_f*)xu[0];
               constexpr bool RX = OCC >= 4;
-              train_pair_packed<PACK, DC, false, TS, 1, XP, RX, CMP, true, false>(
+              train_pair_packed<PACK, DC, TS, 1, XP, RX, CMP, true, false>(
                   a, FP, scr, c, g, xf, xup, ix, acc1, acc2, acc3, acc4, acc2b, acc4b, sq, ab, corr, rows, xr, xu, rd_lo,
                   rd_hi);
             };
@@ -1793,9 +1780,9 @@ __global__ __launch_bounds__(WAVES * 64, OCC) void ae_train_kernel(AEArgs a) {
               rs = rs + 1 == PS ? 0 : rs + 1;
             }
             constexpr bool RX = XM == 1 && OCC >= 4;
-            train_pair_packed<PACK, DC, false, TS, NPW, XP, RX, CMP, XM == 1>(a, FP, scr, c, g, xf, xup, ix, acc1, acc2,
-                                                                              acc3, acc4, acc2b, acc4b, sq, ab, corr,
-                                                                              rows, xr, xu);
+            train_pair_packed<PACK, DC, TS, NPW, XP, RX, CMP, XM == 1>(a, FP, scr, c, g, xf, xup, ix, acc1, acc2,
+                                                                       acc3, acc4, acc2b, acc4b, sq, ab, corr,
+                                                                       rows, xr, xu);
           }
           if (NPW == 2 && pi < npairs) {   // a last lone pair: the oldest of the PS - NPW in flight
             static_assert(NPW == 1 || PS - NPW - 1 >= 0, "ring depth");
@@ -1804,9 +1791,9 @@ __global__ __launch_bounds__(WAVES * 64, OCC) void ae_train_kernel(AEArgs a) {
             float xup[1];
             int ix[1][2];
             load_pair(rs, xf[0], xup[0], ix[0]);
-            train_pair_packed<PACK, DC, false, TS, 1, XP, false, CMP, XM == 1>(a, FP, scr, c, g, xf, xup, ix, acc1, acc2,
-                                                                               acc3, acc4, acc2b, acc4b, sq, ab, corr,
-                                                                               rows);
+            train_pair_packed<PACK, DC, TS, 1, XP, false, CMP, XM == 1>(a, FP, scr, c, g, xf, xup, ix, acc1, acc2,
+                                                                        acc3, acc4, acc2b, acc4b, sq, ab, corr,
+                                                                        rows);
           }
           asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // no DMA may land after the ring is retired
           }
@@ -1860,8 +1847,6 @@ __global__ __launch_bounds__(WAVES * 64, OCC) void ae_train_kernel(AEArgs a) {
         if constexpr (XM == 1) {
           typedef __attribute__((address_space(3))) const unsigned char lds_u8;
           ix = (int)*(lds_u8*)(ring + rd * slotb + 64 * a.D + c);
-        } else if constexpr (XA) {
-          ix = 0;
         }
         rd = rd + 1 == PF ? 0 : rd + 1;
         wr = wr + 1 == PF ? 0 : wr + 1;
@@ -2284,42 +2269,26 @@ __global__ __launch_bounds__(256) void slab_adam_kernel(const float* __restrict_
 // ----------------------------------------------------------------------------
 namespace sml {
 
+// Every SML_AE_* variable ae_train_launch looks at.  The first three are read once per process;
+// the others at every launch (one getenv each per ~1 ms step), so a test can A/B them in one process.
 // SML_AE_RING=0 selects the register-prefetch variant (A/B comparisons).
-static bool ring_pf_enabled() {
-  static const bool on = [] {
-    const char* e = getenv("SML_AE_RING");
-    return !(e && e[0] == '0');
-  }();
-  return on;
-}
-
+// SML_AE_ROUNDS: residency rounds of the pair variants' grid;
+// default 3: 47.05 vs 46.86 (2), 46.17 (1), 46.86 (4) G rows/s (profiles/r02/ilp/rounds)
+// SML_AE_DIRECT_OCC=3: the 3-wave build of the direct step (A/B).  Default the 4-wave one (128 VGPRs,
+// 39 424 B LDS): 45.9 vs 45.3 G fresh rows/s on one box (profiles/r06/serve/fresh_direct_occ*.json)
 // SML_AE_OCC=3|4 picks the waves-per-SIMD variant of the ring kernel.  Default 4:
 // 128 VGPRs, 4 workgroups/CU; on MI355X 27.1 vs 25.7 G rows/s at B = 8M
 // (profiles/r01_v4/sweep_occ*.log).
 // SML_AE_ILP=1|2 picks the one-tile or the tile-pair (train_tiles_ilp, 3 waves/SIMD) loop of
 // the headline variant (reference model, D = 18, tile-packed ring).
-// Both are read at every launch (one getenv per ~1 ms step), so a test can A/B them in one process.
 // Default 3 (packed pairs: 40.4 vs 36.9 G rows/s for the one-tile loop, profiles/r02/ilp);
 // the pair variants always run at 3 waves/SIMD, SML_AE_OCC only picks the one-tile variants'.
-static int train_ilp() {
-  const char* e = getenv("SML_AE_ILP");
-  return (e && (e[0] == '1' || e[0] == '2')) ? e[0] - '0' : 3;
-}
 // SML_AE_DIRECT_PAIRS=0: raw-row steps on the one-tile loop (in-kernel normalise + argmax)
-// instead of the packed-pair loop (A/B; read at every launch like SML_AE_ILP)
-static bool direct_pairs() {
-  const char* e = getenv("SML_AE_DIRECT_PAIRS");
-  return !(e && e[0] == '0');
-}
+// instead of the packed-pair loop (A/B)
 // SML_AE_PAIR_OCC=2|3|4: waves per SIMD (2: two packed pairs per loop iteration) of the packed-pair kernel on the tile-packed ring
-// (read at every launch, like SML_AE_ILP)
 // Default 4: 4 waves per SIMD, forward operands through early LDS writes and backward
 // ones through the MFMA identity (XP 3) -- 51.6-53.4 vs 48.6-49.5 G rows/s for the round-5 loop
 // (3, XP 0) on the same boxes (profiles/r06/SUMMARY.md §1).
-static int pair_occ() {
-  const char* e = getenv("SML_AE_PAIR_OCC");
-  return (e && (e[0] == '2' || e[0] == '3' || e[0] == '4')) ? e[0] - '0' : 4;
-}
 // SML_AE_PAIR_XP=0|1|2|3|4|5: the packed-pair weight-gradient operand path (train_pair_packed's XP);
 // at SML_AE_PAIR_OCC=4, 0 means 1 (the 4-wave build needs the early writes' registers).  4 (the
 // early backward writes, TS 12) and 5 (4 with the lane masks in the read addresses) are built for
@@ -2329,17 +2298,32 @@ static int pair_occ() {
 // vs 56.24-56.53 on another box, bit-identical results; 14 VALU fewer and 4 LDS reads more per trip,
 // SQ_WAIT_INST_LDS rises from 232 to 300 cycles per trip and the wave still spends 88 cycles fewer
 // in a trip (profiles/r17/mask_reads/SUMMARY.md).
-static int pair_xp() {
-  const char* e = getenv("SML_AE_PAIR_XP");
-  return (e && e[0] >= '0' && e[0] <= '5') ? e[0] - '0' : 5;
+static AETrainKnobs ae_train_knobs() {
+  // the variable's first character where it is one of lo..hi, as a number; dflt otherwise
+  auto digit = [](const char* name, char lo, char hi, int dflt) {
+    const char* e = getenv(name);
+    return (e && e[0] >= lo && e[0] <= hi) ? e[0] - '0' : dflt;
+  };
+  static const AETrainKnobs once = [&] {
+    AETrainKnobs k{};
+    k.ring = digit("SML_AE_RING", '0', '0', 1) != 0;
+    const char* e = getenv("SML_AE_ROUNDS");
+    const int r = e ? std::atoi(e) : 3;
+    k.rounds = r >= 1 && r <= 8 ? r : 3;
+    k.direct_occ = digit("SML_AE_DIRECT_OCC", '3', '3', 4);
+    return k;
+  }();
+  AETrainKnobs k = once;
+  k.ilp = digit("SML_AE_ILP", '1', '2', 3);
+  k.direct_pairs = digit("SML_AE_DIRECT_PAIRS", '0', '0', 1) != 0;
+  k.pair_occ = digit("SML_AE_PAIR_OCC", '2', '4', 4);
+  k.pair_xp = digit("SML_AE_PAIR_XP", '0', '5', 5);
+  k.occ = digit("SML_AE_OCC", '3', '3', 4);
+  return k;
 }
-static int train_occupancy() {
-  const char* e = getenv("SML_AE_OCC");
-  return (e && e[0] == '3') ? 3 : 4;
-}
-// The host sizes its partials buffer for 2 x this many workgroups per CU (the largest grid
-// of any variant: the pair variants' 3 rounds x 3 resident = 9 <= 10); the launcher trims
-// the grid to the launched variant's own rounds x residency.
+// The host sizes its partials buffer for 2 x this many workgroups per CU (16: above the largest
+// default grid of any variant, the 4-wave pair variants' 3 rounds x 4 resident = 12); the launcher
+// trims the grid it is given to the launched variant's own rounds x residency.
 int ae_train_blocks_per_cu() { return 8; }
 static int device_cus() {
   static const int cus = [] {
@@ -2380,6 +2364,11 @@ int ae_train_grid(int64_t n, int max_blocks) {
   return (int)blocks;
 }
 
+// the kernel of every row of kAEVariants, in the table's order
+#define SML_AE_KERNEL(V) ae_train_kernel<aev::V>,
+static void (*const kAETrainKernels[kAEVariantCount])(AEArgs) = {SML_AE_TRAIN_VARIANTS(SML_AE_KERNEL)};
+#undef SML_AE_KERNEL
+
 hipError_t ae_train_launch(const float* x, int64_t n, int64_t ld, const float* scale, const float* shift,
                            const float* params, float* partials, int64_t* iter, const int64_t* cursor,
                            const int* dims, const int* acts, float l1, int want_acc, int grid, const uint8_t* xpack,
@@ -2390,143 +2379,24 @@ hipError_t ae_train_launch(const float* x, int64_t n, int64_t ld, const float* s
   a.D = dims[0]; a.n1 = dims[1]; a.n2 = dims[2]; a.n3 = dims[3];
   a.a1 = acts[0]; a.a2 = acts[1]; a.a3 = acts[2]; a.a4 = acts[3];
   a.l1 = l1; a.want_acc = want_acc;
-  const bool vec = ((ld & 1) == 0) && ((dims[0] & 1) == 0) && dims[0] >= 2 &&
-                   ((reinterpret_cast<uintptr_t>(x) & 7) == 0);
-  // LDS-DMA ring: contiguous rows, 17 <= D <= 31 (two DMAs per tile), 16-B aligned
-  // tiles (the ring cursor moves in whole batches, so n * ld * 4 must stay 16-B aligned)
-  const int D = dims[0];
-  const bool ring_ok = vec && ld == D && D >= 17 && D <= 31 && ((reinterpret_cast<uintptr_t>(x) & 15) == 0) &&
-                       (cursor == nullptr || ((n * ld) & 3) == 0) && ring_pf_enabled();
-  const int pack = acts[0] | (acts[1] << 2) | (acts[2] << 4) | (acts[3] << 6);
-  const dim3 bd(WAVES * 64);
-  const int occ = train_occupancy();
-  const int grid_in = grid;
-  dim3 gd(grid);
-  auto set_grid = [&](int cap) {
-    grid = grid_in < cap ? grid_in : cap;
-    *grid_used = grid;
-    gd = dim3(grid);
-  };
-  set_grid(2 * occ * device_cus());   // one-tile variants: two rounds of their residency
-  // the pair variants hold 3 workgroups per CU.  SML_AE_ROUNDS: residency rounds of their grid;
-  // default 3: 47.05 vs 46.86 (2), 46.17 (1), 46.86 (4) G rows/s (profiles/r02/ilp/rounds)
-  auto pair_grid = [&](int occ_pairs = 3) {
-    static const int rounds = [] {
-      const char* e = std::getenv("SML_AE_ROUNDS");
-      const int r = e ? std::atoi(e) : 3;
-      return r >= 1 && r <= 8 ? r : 3;
-    }();
-    set_grid(rounds * occ_pairs * device_cus());
-  };
-  // the 4-wave compact-ring pair instances say which of them ran (ae_train_last_variant)
+  AETrainRequest r{};
+  r.pack = acts[0] | (acts[1] << 2) | (acts[2] << 4) | (acts[3] << 6);
+  r.D = dims[0]; r.n1 = dims[1]; r.n2 = dims[2]; r.n3 = dims[3];
+  r.n = n; r.ld = ld;
+  r.want_acc = want_acc != 0; r.has_cursor = cursor != nullptr; r.has_xpack = xpack != nullptr;
+  r.x_addr = (unsigned)(reinterpret_cast<uintptr_t>(x) & 15);
+  r.xpack_addr = (unsigned)(reinterpret_cast<uintptr_t>(xpack) & 15);
+  r.xpack_live = xpack_live;
+  const AETrainKnobs k = ae_train_knobs();
   last_variant = LastVariant{};
-  auto launch_noted = [&](void (*kern)(AEArgs), int xp_, int ts_) {
-    last_variant = LastVariant{reinterpret_cast<const void*>(kern), xp_, ts_};
-    hipLaunchKernelGGL(kern, gd, bd, 0, stream, a);
-  };
-  if (pack == PACK_REF) {
-    // tile-packed ring with ingest-time x argmax (pack_tiles_argmax): whole 16-row tiles
-    const bool xa_ok = xpack != nullptr && want_acc && (n & 15) == 0 &&
-                       ((reinterpret_cast<uintptr_t>(xpack) & 15) == 0);
-    static const int probe = [] {
-      const char* e = std::getenv("SML_AE_XPROBE");
-      return e ? std::atoi(e) : 0;
-    }();
-    // A caller that passes a tile-packed ring may have packed it from rows other than x's (an
-    // epoch's shuffle fused into the pack: FusedAE.pack_ring); only the XM 1 variants read it,
-    // so refuse to silently train on x when none of them applies.
-    // xpack_live: the features the packed ring stores (0 = all D).  Only the packed-pair variants
-    // read the compact ring of the cardata live set; any other mask, or any other variant, is refused.
-    // That mask means the LANE-ORDERED compact layout (pack_tiles_argmax with lane_order, what
-    // FusedAE builds): no kernel reads the ascending compact layout.
-    // the pair loops count pairs in 32 bits (2^30 pairs = 2^35 rows: past any device's memory)
-    if ((n >> 5) >= (int64_t(1) << 30)) return hipErrorInvalidValue;
-    const bool pairs_ok = ((n >> 4) & 1) == 0 && train_ilp() == 3 && dims[1] <= 15 && dims[2] <= 7 && dims[3] <= 7;
-    const bool full = xpack_live == 0 || (D <= 31 && xpack_live == (1u << D) - 1u);
-    const bool cm = !full && D == 18 && xpack_live == kLiveCardata;
-    if (xpack != nullptr && !full && !cm) return hipErrorInvalidValue;
-    const bool xpack_used = xa_ok && ring_ok && D == 18 && (cm ? pairs_ok : (train_ilp() == 2 || pairs_ok || occ == 4));
-    if (xpack != nullptr && !xpack_used && (probe < 2 || cm)) return hipErrorInvalidValue;
-    if (ring_ok && occ == 4 && D == 18 && want_acc && probe == 2)
-      hipLaunchKernelGGL((ae_train_kernel<PACK_REF, true, 3, 4, 18, 2>), gd, bd, 0, stream, a);
-    else if (ring_ok && occ == 4 && D == 18 && want_acc && probe == 3)
-      hipLaunchKernelGGL((ae_train_kernel<PACK_REF, true, 3, 4, 18, 3>), gd, bd, 0, stream, a);
-    else if (ring_ok && D == 18 && xa_ok && train_ilp() == 2) {
-      pair_grid();
-      hipLaunchKernelGGL((ae_train_kernel<PACK_REF, true, 6, 3, 18, 1, 2>), gd, bd, 0, stream, a);
-    } else if (ring_ok && D == 18 && xa_ok && ((n >> 4) & 1) == 0 && train_ilp() == 3 && dims[1] <= 15 &&
-               dims[2] <= 7 && dims[3] <= 7) {   // packed pairs: an even number of whole tiles
-      const int po = pair_occ();
-      pair_grid(po);
-      const int xp = pair_xp();
-      if (cm) {   // the compact-ring twin of every variant below, and the XP 4 instance
-        if (po == 2)
-          hipLaunchKernelGGL((ae_train_kernel<PACK_REF, true, 8, 2, 18, 1, 3, 10, 2, 0, 1>), gd, bd, 0, stream, a);
-        else if (po == 4 && xp == 5)   // XP 4 with the lane masks in the read addresses: 40 480 B
-          launch_noted(ae_train_kernel<PACK_REF, true, 4, 4, 18, 1, 3, 12, 1, 5, 1>, 5, 12);
-        else if (po == 4 && xp == 4)   // TS 12: 39 424 B, still four workgroups per CU
-          launch_noted(ae_train_kernel<PACK_REF, true, 4, 4, 18, 1, 3, 12, 1, 4, 1>, 4, 12);
-        else if (po == 4 && xp >= 2)
-          launch_noted(ae_train_kernel<PACK_REF, true, 4, 4, 18, 1, 3, 10, 1, 3, 1>, 3, 10);
-        else if (xp >= 3)
-          hipLaunchKernelGGL((ae_train_kernel<PACK_REF, true, 6, 3, 18, 1, 3, 10, 1, 3, 1>), gd, bd, 0, stream, a);
-        else if (po == 4)
-          hipLaunchKernelGGL((ae_train_kernel<PACK_REF, true, 4, 4, 18, 1, 3, 10, 1, 1, 1>), gd, bd, 0, stream, a);
-        else if (xp == 1)
-          hipLaunchKernelGGL((ae_train_kernel<PACK_REF, true, 6, 3, 18, 1, 3, 10, 1, 1, 1>), gd, bd, 0, stream, a);
-        else if (xp == 2)
-          hipLaunchKernelGGL((ae_train_kernel<PACK_REF, true, 6, 3, 18, 1, 3, 10, 1, 2, 1>), gd, bd, 0, stream, a);
-        else
-          hipLaunchKernelGGL((ae_train_kernel<PACK_REF, true, 6, 3, 18, 1, 3, 10, 1, 0, 1>), gd, bd, 0, stream, a);
-      } else if (po == 2)   // two packed pairs per iteration, 2 waves / SIMD
-        hipLaunchKernelGGL((ae_train_kernel<PACK_REF, true, 8, 2, 18, 1, 3, 10, 2>), gd, bd, 0, stream, a);
-      else if (po == 4 && xp >= 2)   // (XP 2 at 4 waves spills: the MFMA-transpose temporaries)
-        hipLaunchKernelGGL((ae_train_kernel<PACK_REF, true, 4, 4, 18, 1, 3, 10, 1, 3>), gd, bd, 0, stream, a);
-      else if (xp >= 3)
-        hipLaunchKernelGGL((ae_train_kernel<PACK_REF, true, 6, 3, 18, 1, 3, 10, 1, 3>), gd, bd, 0, stream, a);
-      else if (po == 4)
-        hipLaunchKernelGGL((ae_train_kernel<PACK_REF, true, 4, 4, 18, 1, 3, 10, 1, 1>), gd, bd, 0, stream, a);
-      else if (xp == 1)
-        hipLaunchKernelGGL((ae_train_kernel<PACK_REF, true, 6, 3, 18, 1, 3, 10, 1, 1>), gd, bd, 0, stream, a);
-      else if (xp == 2)
-        hipLaunchKernelGGL((ae_train_kernel<PACK_REF, true, 6, 3, 18, 1, 3, 10, 1, 2>), gd, bd, 0, stream, a);
-      else
-        hipLaunchKernelGGL((ae_train_kernel<PACK_REF, true, 6, 3, 18, 1, 3>), gd, bd, 0, stream, a);
-    }
-    else if (ring_ok && occ == 4 && D == 18 && xa_ok)
-      hipLaunchKernelGGL((ae_train_kernel<PACK_REF, true, 3, 4, 18, 1>), gd, bd, 0, stream, a);
-    else if (ring_ok && D == 18 && xpack == nullptr && (n & 31) == 0 && train_ilp() == 3 && direct_pairs() &&
-             dims[1] <= 15 && dims[2] <= 7 && dims[3] <= 7) {
-      // rows trained once (fresh / streamed): packed pairs straight from the raw rows,
-      // normalize_fn + argmax(x) in registers (no K8 pack pass)
-      // SML_AE_DIRECT_OCC=3: the 3-wave build (A/B).  Default the 4-wave one (128 VGPRs, 39 424 B
-      // LDS): 45.9 vs 45.3 G fresh rows/s on one box (profiles/r06/serve/fresh_direct_occ*.json)
-      static const int docc = [] {
-        const char* e = std::getenv("SML_AE_DIRECT_OCC");
-        return (e && e[0] == '3') ? 3 : 4;
-      }();
-      pair_grid(docc);
-      if (docc == 4)
-        hipLaunchKernelGGL((ae_train_kernel<PACK_REF, true, 4, 4, 18, 0, 3, 10, 1, 3>), gd, bd, 0, stream, a);
-      else if (pair_xp() >= 3)
-        hipLaunchKernelGGL((ae_train_kernel<PACK_REF, true, 6, 3, 18, 0, 3, 10, 1, 3>), gd, bd, 0, stream, a);
-      else
-        hipLaunchKernelGGL((ae_train_kernel<PACK_REF, true, 6, 3, 18, 0, 3>), gd, bd, 0, stream, a);
-    }
-    else if (ring_ok && occ == 4 && D == 18)  // the cardata-v1 reference model: D fixed at compile time
-      hipLaunchKernelGGL((ae_train_kernel<PACK_REF, true, 3, 4, 18>), gd, bd, 0, stream, a);
-    else if (ring_ok && occ == 4 && 3 * 64 * D <= ring_bytes<4>())
-      hipLaunchKernelGGL((ae_train_kernel<PACK_REF, true, 3, 4>), gd, bd, 0, stream, a);
-    else if (ring_ok && occ == 4)
-      hipLaunchKernelGGL((ae_train_kernel<PACK_REF, true, 2, 4>), gd, bd, 0, stream, a);
-    else if (ring_ok && 5 * 64 * D <= ring_bytes<3>())
-      hipLaunchKernelGGL((ae_train_kernel<PACK_REF, true, 5, 3>), gd, bd, 0, stream, a);
-    else if (ring_ok) hipLaunchKernelGGL((ae_train_kernel<PACK_REF, true, 3, 3>), gd, bd, 0, stream, a);
-    else if (vec) hipLaunchKernelGGL((ae_train_kernel<PACK_REF, true, 0, 3>), gd, bd, 0, stream, a);
-    else hipLaunchKernelGGL((ae_train_kernel<PACK_REF, false, 0, 3>), gd, bd, 0, stream, a);
-  } else {
-    hipLaunchKernelGGL((ae_train_kernel<PACK_DYN, false, 0, 3>), gd, bd, 0, stream, a);
-  }
+  const AEVariantRow* v = ae_train_select(r, k);
+  if (v == nullptr) return hipErrorInvalidValue;
+  const int cap = ae_train_grid_cap(*v, k, device_cus());
+  *grid_used = grid < cap ? grid : cap;
+  void (*const kern)(AEArgs) = kAETrainKernels[v - kAEVariants];
+  // the 4-wave compact-ring pair instances say which of them ran (ae_train_last_variant)
+  if (v->xp_noted >= 0) last_variant = LastVariant{reinterpret_cast<const void*>(kern), v->xp_noted, v->ts_noted};
+  hipLaunchKernelGGL(kern, dim3(*grid_used), dim3(WAVES * 64), 0, stream, a);
   return hipGetLastError();
 }
 

@@ -22,7 +22,7 @@ SO = os.path.join(PKG, "_C.so")
 # Kernels allowed a private segment: the fully dynamic dense-AE fallback (runtime
 # activation codes, unvectorised loads) -- never taken by the reference models, which
 # compile their activations in (PACK_REF).
-ALLOWED = (r"ae_train_kernelILin1ELb0ELi0ELi3E",)
+ALLOWED = (r"ae_train_kernelIN3sml3aev7DynamicEEE",)
 
 
 def _kernel_scratch(so_path, tmp_path):
