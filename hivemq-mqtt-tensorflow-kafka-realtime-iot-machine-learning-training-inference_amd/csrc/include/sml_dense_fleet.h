@@ -1,5 +1,6 @@
 // What differs between the members of a fleet of Dense stacks, for the kernel bodies of
-// dense_minibatch.hip and dense_minibatch_bf16.hip (sml_dense_mb_body.h, sml_dense_mb_bf16_body.h).  A
+// dense_minibatch.hip and dense_minibatch_bf16.hip (sml_dense_mb_body.h, sml_dense_mb_bf16_body.h) and
+// for the row staging they share (stage_load of sml_dense_mb_dev.h).  A
 // body reads what a fleet shares (layer table, plan, batch, Adam constants) from the launch's
 // DenseMBArgs where they are, in the kernel arguments, and everything else from `run`: the arguments
 // themselves in a single-model entry, a DenseMBRun in a fleet entry, rebased once per workgroup from

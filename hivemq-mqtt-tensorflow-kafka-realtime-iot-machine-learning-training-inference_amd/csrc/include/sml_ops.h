@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "sml_dense_mb_plan.h"
+
 namespace sml {
 
 // ---- dense autoencoder (ae_fused.hip) ----
@@ -394,42 +396,8 @@ hipError_t dense_serve_launch(const DenseServeArgs& args, hipStream_t stream);
 // accuracy, backward, gradients, Adam) of a stack described by a table.  fp32 throughout; the
 // weights stay in LDS and every thread keeps the gradient and Adam moments of up to DMB_TPT 4x4
 // tiles of the kernels (and, for the tiles of a kernel's first four rows, of four bias elements)
-// in registers.
-enum : int {
-  DMB_MAXLAYERS = 8,
-  DMB_MAXW = 128,             // units / inputs of a layer
-  DMB_MAXBATCH = 128,
-  DMB_NT = 512,               // threads of the workgroup
-  DMB_TPT = 2,                // 4x4 parameter tiles a thread can own
-  DMB_CHUNK = 32,             // rows of a batch in LDS at a time
-  DMB_MAXPARAMS = DMB_NT * DMB_TPT * 16,   // kernel elements with both widths rounded up to 4
-  DMB_LDS_BYTES = 160 * 1024
-};
-struct DenseMBLayer {
-  int in, units;
-  int act;             // ACT_* code
-  int has_bias;
-  float l1, l2;        // activity regulariser of the layer's output
-  int w_off, b_off;    // float offsets of the [in, units] kernel and the bias in flat / m / v
-};
-// where the kernel keeps a layer in LDS (float offsets), derived from the table alone
-struct DenseMBLayerPlan {
-  int ip, up;          // in / units rounded up to 4
-  int ws;              // floats between two rows of the kernel image (up, or up + 4: see the kernel)
-  int lw, lb;          // kernel image [ip][ws], bias [up]
-  int la, ld;          // the layer's output [DMB_CHUNK][up] and its gradient (the last layer's share one buffer)
-  int tile0;           // first 4x4 tile (= owning thread) of the layer
-};
-struct DenseMBPlan {
-  int dp;              // input width rounded up to 4
-  int la0;             // input rows [DMB_CHUNK][dp]
-  int lyt;             // target rows [DMB_CHUNK][op] (= la0 when y is null)
-  int lstat;           // per-row loss / correct / penalty, then the step's totals
-  int wimg0, wimg1;    // the weight image (zero-filled at launch)
-  int ntiles;
-  int lds_floats;
-  DenseMBLayerPlan L[DMB_MAXLAYERS];
-};
+// in registers.  The limits, DenseMBLayer, the LDS plans of both precisions and dense_mb_check are
+// in sml_dense_mb_plan.h (plain C++, also for host programs).
 struct DenseMBArgs {
   float* flat;
   float* m;
@@ -449,11 +417,6 @@ struct DenseMBArgs {
   float* out;          // [nsteps, 2]
   int precision;       // DMB_FP32 (dense_minibatch.hip) or DMB_BF16 (dense_minibatch_bf16.hip)
 };
-// empty if the kernel of this precision can train the stack (D inputs, nl layers, parameter offsets
-// inside nflat floats, this batch size, targets of their own or y = x), else the limit it exceeds
-const char* dense_mb_check(const DenseMBLayer* L, int nl, int D, int batch, int64_t nflat, bool own_targets,
-                           int precision = 0);
-DenseMBPlan dense_mb_plan(const DenseMBLayer* L, int nl, int D, bool own_targets);
 // dispatches on args.precision
 hipError_t dense_mb_launch(DenseMBArgs args, hipStream_t stream);
 
@@ -461,36 +424,6 @@ hipError_t dense_mb_launch(DenseMBArgs args, hipStream_t stream);
 // fp32 master weights, gradients and Adam moments live in the registers of the wave that owns a
 // 16x16 tile of a kernel (MFMA C layout); LDS holds one bf16 image of the weights, re-derived from
 // the masters after every Adam, and the chunk's activations and gradients.
-enum : int {
-  DMB_FP32 = 0,
-  DMB_BF16 = 1,
-  DMB_TILES_BF16 = 64,                        // 16x16 parameter tiles: 8 per wave
-  DMB_MAXPARAMS_BF16 = DMB_TILES_BF16 * 256   // kernel elements with both widths rounded up to 16
-};
-// byte offsets from the start of the dynamic LDS, all multiples of 16
-struct DenseMBLayerPlanBF16 {
-  int ip, up;          // in / units rounded up to 16
-  int ws;              // bf16 elements between two rows of the weight image [up][ws] (unit-major), ip + 8
-  int lw;              // the weight image
-  int lb;              // fp32 bias, its two Adam moments and its gradient: 4 x [up]
-  int hs, la;          // the layer's fp32 output [DMB_CHUNK][hs], hs = up + 4; overwritten by its fp32 gradient
-  int bs;              // bf16 elements between two rows of the bf16 images, up + 8
-  int lhb;             // bf16 output [DMB_CHUNK][bs] (the last layer has none)
-  int ld;              // bf16 pre-activation gradient [DMB_CHUNK][bs]
-  int tile0;           // first 16x16 tile of the layer; tile t belongs to wave t % 8, slot t / 8
-};
-struct DenseMBPlanBF16 {
-  int dp;              // input width rounded up to 16
-  int xs, la0;         // fp32 input rows [DMB_CHUNK][xs], xs = dp + 4
-  int xbs, lxb;        // bf16 input rows [DMB_CHUNK][xbs], xbs = dp + 8
-  int ys, lyt;         // fp32 target rows [DMB_CHUNK][ys] (= the input rows when y is null)
-  int lstat;           // per-row loss / correct / penalty, then the step's totals
-  int ltile;           // DMB_TILES_BF16 ints: layer << 16 | input block << 8 | unit block
-  int ntiles;
-  int lds_bytes;
-  DenseMBLayerPlanBF16 L[DMB_MAXLAYERS];
-};
-DenseMBPlanBF16 dense_mb_plan_bf16(const DenseMBLayer* L, int nl, int D, bool own_targets);
 hipError_t dense_mb_launch_bf16(const DenseMBArgs& args, hipStream_t stream);   // args checked by dense_mb_launch
 
 // ---- fleets: M models of ONE architecture, workgroup b trains model sched[b] (both kernel files) ----

@@ -29,29 +29,22 @@
 // The kernel waits on nothing outside the workgroup: every loop bound is known at launch.
 // That is what lets dense_mb_fleet_kernel run M models of one architecture side by side, workgroup b
 // on model sched[b] (sml_dense_fleet.h): the same body (sml_dense_mb_body.h) on rebased arguments.
+// What this kernel has in common with its bf16 sibling is not here: the limits, the plan and the
+// check in sml_dense_mb_plan.h; row staging, the loss phase's penalty sum and row merge, and the
+// launch sequence in sml_dense_mb_dev.h.
 #include "sml_common.h"
 #include "sml_ops.h"
 
 #include "sml_adam.h"
 #include "sml_dense_fleet.h"
+#include "sml_dense_mb_dev.h"
 
-#include <string>
 #include <type_traits>
 
 namespace sml {
 namespace {
 
-constexpr int NT = DMB_NT, CH = DMB_CHUNK;
-constexpr int STAT_SQ = 0, STAT_OK = CH, STAT_PEN = 2 * CH, STAT_TOT = 3 * CH;   // floats from lstat
-
-__device__ __forceinline__ f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
-__device__ __forceinline__ void st4(float* p, f32x4 v) { *reinterpret_cast<f32x4*>(p) = v; }
-
-// d(l1 * |h| + l2 * h^2) / dh, divided by the step's rows as Keras does
-__device__ __forceinline__ float pen_grad(float l1, float l2, float h, float inv_rows) {
-  const float sg = h > 0.0f ? 1.0f : h < 0.0f ? -1.0f : 0.0f;
-  return (l1 * sg + 2.0f * l2 * h) * inv_rows;
-}
+using namespace dmb;
 
 // layer output for `rows` rows of the chunk: thread tile = RT rows x 4 units, k ascending
 template <int RT>
@@ -142,40 +135,6 @@ __device__ __forceinline__ void by_row_tile(int rows, int nq, F&& f) {
   else f(std::integral_constant<int, 1>{});
 }
 
-// rows of one chunk on their way from global memory to LDS: row tid / LPR, columns tid % LPR + LPR e
-constexpr int LPR = NT / CH;            // lanes per row in the staging and loss phases
-constexpr int SE = DMB_MAXW / LPR;      // elements per lane of a row
-static_assert(LPR * CH == NT && LPR <= 32 && (LPR & (LPR - 1)) == 0 && SE * LPR == DMB_MAXW, "row phases: lanes per row");
-struct Stage {
-  float x[SE], y[SE];
-};
-
-template <typename Run>
-__device__ __forceinline__ void stage_load(const DenseMBArgs& a, const Run& run, int O, int s, int k, int steps, Stage& st) {
-  const int r = threadIdx.x / LPR, q = threadIdx.x % LPR;
-  int rows = 0;
-  int64_t pos = 0;
-  if (s < steps) {
-    const int64_t base = run.row0 + (int64_t)s * a.batch;
-    const int64_t left = run.n - base;
-    const int rows_s = left < a.batch ? (int)left : a.batch;
-    rows = rows_s - k * CH < CH ? rows_s - k * CH : CH;
-    pos = base + k * CH + r;
-  }
-  const bool rv = r < rows;
-  int64_t src = 0;
-  if (rv) {
-    src = run.order ? (int64_t)run.order[pos] : pos;
-    src = src < 0 ? 0 : src >= run.n ? run.n - 1 : src;
-  }
-#pragma unroll
-  for (int e = 0; e < SE; ++e) {
-    const int c = q + LPR * e;
-    st.x[e] = (rv && c < a.D) ? run.x[src * a.ldx + c] : 0.0f;
-    st.y[e] = (run.y != nullptr && rv && c < O) ? run.y[src * a.ldy + c] : 0.0f;
-  }
-}
-
 template <typename Run>
 __device__ __forceinline__ void stage_store(float* S, const DenseMBArgs& a, const Run& run, int op, const Stage& st) {
   const int r = threadIdx.x / LPR, q = threadIdx.x % LPR;
@@ -193,18 +152,7 @@ __device__ __forceinline__ void loss_phase(float* S, const DenseMBLayer* sL, con
                                            int lstat, int rows, float inv_n, float inv_rows) {
   const int r = threadIdx.x / LPR, q = threadIdx.x % LPR;
   const bool rv = r < rows;
-  float pen = 0.0f;
-  for (int l = 0; l < nl; ++l) {
-    const float l1 = sL[l].l1, l2 = sL[l].l2;
-    if (l1 == 0.0f && l2 == 0.0f) continue;
-    float s1 = 0.0f, s2 = 0.0f;
-    for (int j = q; j < sL[l].units; j += LPR) {
-      const float h = S[sP[l].la + r * sP[l].up + j];
-      s1 += fabsf(h);
-      s2 = fmaf(h, h, s2);
-    }
-    pen += l1 * s1 + l2 * s2;
-  }
+  const float pen = pen_sum(sL, nl, q, [&](int l) { return S + sP[l].la + r * sP[l].up; });
   const DenseMBLayer& L = sL[nl - 1];
   const DenseMBLayerPlan& P = sP[nl - 1];
   const bool lpen = L.l1 != 0.0f || L.l2 != 0.0f;
@@ -225,20 +173,7 @@ __device__ __forceinline__ void loss_phase(float* S, const DenseMBLayer* sL, con
     if (lpen) g += pen_grad(L.l1, L.l2, yv, inv_rows);
     yrow[j] = valid ? act_grad(L.act, yv, g) : 0.0f;
   }
-#pragma unroll
-  for (int o = LPR / 2; o > 0; o >>= 1) {
-    sq += __shfl_xor(sq, o, 64);
-    pen += __shfl_xor(pen, o, 64);
-    const float oy = __shfl_xor(by, o, 64), ot = __shfl_xor(bt, o, 64);
-    const int oiy = __shfl_xor(iy, o, 64), oit = __shfl_xor(it, o, 64);
-    if (oy > by || (oy == by && oiy < iy)) { by = oy; iy = oiy; }
-    if (ot > bt || (ot == bt && oit < it)) { bt = ot; it = oit; }
-  }
-  if (q == 0) {
-    S[lstat + STAT_SQ + r] = rv ? sq : 0.0f;
-    S[lstat + STAT_OK + r] = (rv && iy == it) ? 1.0f : 0.0f;
-    S[lstat + STAT_PEN + r] = rv ? pen : 0.0f;
-  }
+  row_stats(S + lstat, r, q, rv, sq, pen, by, iy, bt, it);
 }
 
 // one owned 4x4 tile: where it sits, and its state for the whole launch
@@ -296,137 +231,26 @@ __global__ __launch_bounds__(NT) void dense_mb_fleet_kernel(const DenseMBArgs a,
 #include "sml_dense_mb_body.h"
 }
 
-constexpr int pad4(int n) { return (n + 3) / 4 * 4; }
-constexpr int STATIC_LDS = 1024;   // the kernel's layer table copy, rounded up
+// what both launchers refuse before they look at the precision
+bool launchable(const DenseMBArgs& a, int64_t nflat) {
+  return a.nsteps >= 1 && dense_mb_check(a.L, a.nl, a.D, a.batch, nflat, a.y != nullptr, a.precision).empty();
+}
 
 }  // namespace
 
-DenseMBPlan dense_mb_plan(const DenseMBLayer* L, int nl, int D, bool own_targets) {
-  DenseMBPlan P{};
-  int off = 0, tiles = 0;
-  P.dp = pad4(D);
-  P.la0 = off;
-  off += CH * P.dp;
-  P.wimg0 = off;
-  int prev = P.dp;
-  for (int l = 0; l < nl; ++l) {
-    DenseMBLayerPlan& q = P.L[l];
-    q.ip = prev;
-    q.up = pad4(L[l].units);
-    q.ws = ((q.up >> 2) & 1) ? q.up : q.up + 4;
-    q.lw = off;
-    off += q.ip * q.ws;
-    q.lb = off;
-    off += q.up;
-    q.tile0 = tiles;
-    tiles += (q.ip >> 2) * (q.up >> 2);
-    prev = q.up;
-  }
-  P.wimg1 = off;
-  for (int l = 0; l < nl; ++l) {
-    P.L[l].la = off;
-    off += CH * P.L[l].up;
-  }
-  for (int l = 0; l < nl; ++l) {
-    if (l == nl - 1) {
-      P.L[l].ld = P.L[l].la;
-    } else {
-      P.L[l].ld = off;
-      off += CH * P.L[l].up;
-    }
-  }
-  if (own_targets) {
-    P.lyt = off;
-    off += CH * prev;
-  } else {
-    P.lyt = P.la0;
-  }
-  P.lstat = off;
-  off += 4 * CH;
-  P.ntiles = tiles;
-  P.lds_floats = off;
-  return P;
-}
-
-const char* dense_mb_check(const DenseMBLayer* L, int nl, int D, int batch, int64_t nflat, bool own_targets,
-                           int precision) {
-  static thread_local std::string why;
-  why.clear();
-  auto fail = [&](std::string s) {
-    why = std::move(s);
-    return why.c_str();
-  };
-  if (precision != DMB_FP32 && precision != DMB_BF16)
-    return fail("precision " + std::to_string(precision) + " is neither fp32 (0) nor bf16 (1)");
-  const bool bf16 = precision == DMB_BF16;
-  auto pad = [&](int n) { return bf16 ? (n + 15) / 16 * 16 : pad4(n); };
-  if (nl < 1 || nl > DMB_MAXLAYERS)
-    return fail(std::to_string(nl) + " Dense layers: the persistent trainer takes 1.." + std::to_string(DMB_MAXLAYERS) +
-                " (MAX_LAYERS)");
-  if (batch < 1 || batch > DMB_MAXBATCH)
-    return fail("batch " + std::to_string(batch) + " is outside 1.." + std::to_string(DMB_MAXBATCH) + " (MAX_BATCH)");
-  if (D < 1 || D > DMB_MAXW)
-    return fail("input width " + std::to_string(D) + " is outside 1.." + std::to_string(DMB_MAXW) + " (MAX_WIDTH)");
-  int prev = D;
-  int64_t padded = 0;
-  for (int l = 0; l < nl; ++l) {
-    if (L[l].in != prev) return fail("layer " + std::to_string(l) + " does not take the previous layer's width");
-    if (L[l].units < 1 || L[l].units > DMB_MAXW)
-      return fail("layer " + std::to_string(l) + " has " + std::to_string(L[l].units) + " units: the limit is " +
-                  std::to_string(DMB_MAXW) + " (MAX_WIDTH)");
-    if (L[l].act < ACT_LINEAR || L[l].act > ACT_SIGMOID) return fail("layer " + std::to_string(l) + ": unknown activation");
-    const int64_t nw = (int64_t)L[l].in * L[l].units;
-    if (L[l].w_off < 0 || L[l].w_off + nw > nflat ||
-        (L[l].has_bias && (L[l].b_off < 0 || (int64_t)L[l].b_off + L[l].units > nflat)))
-      return fail("layer " + std::to_string(l) + ": parameter offsets outside the flat buffer");
-    padded += (int64_t)pad(L[l].in) * pad(L[l].units);
-    prev = L[l].units;
-  }
-  if (bf16 && padded > DMB_MAXPARAMS_BF16)
-    return fail(std::to_string(padded) + " kernel elements (widths rounded up to 16): the limit is " +
-                std::to_string(DMB_MAXPARAMS_BF16) + " (MAX_PARAMS_BF16)");
-  if (!bf16 && padded > DMB_MAXPARAMS)
-    return fail(std::to_string(padded) + " kernel elements (widths rounded up to 4): the limit is " +
-                std::to_string(DMB_MAXPARAMS) + " (MAX_PARAMS)");
-  if (!own_targets && prev != D) return fail("y = x needs as many output units as inputs");
-  const int64_t need = (bf16 ? (int64_t)dense_mb_plan_bf16(L, nl, D, own_targets).lds_bytes
-                             : (int64_t)dense_mb_plan(L, nl, D, own_targets).lds_floats * 4) + STATIC_LDS;
-  if (need > DMB_LDS_BYTES)
-    return fail(std::to_string(need) + " bytes of LDS: the limit is " + std::to_string(DMB_LDS_BYTES) + " (LDS_BYTES)");
-  return "";
-}
-
 hipError_t dense_mb_launch(DenseMBArgs a, hipStream_t stream) {
-  const bool own_targets = a.y != nullptr;
-  if (dense_mb_check(a.L, a.nl, a.D, a.batch, INT64_MAX, own_targets, a.precision)[0] != 0) return hipErrorInvalidValue;
-  if (a.nsteps < 1 || a.row0 < 0 || a.row0 >= a.n) return hipErrorInvalidValue;
+  if (!launchable(a, INT64_MAX) || a.row0 < 0 || a.row0 >= a.n) return hipErrorInvalidValue;
   if (a.precision == DMB_BF16) return dense_mb_launch_bf16(a, stream);
-  a.P = dense_mb_plan(a.L, a.nl, a.D, own_targets);
-  const size_t lds = sizeof(float) * (size_t)a.P.lds_floats;
-  if (lds > 65536) {
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(dense_mb_kernel),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-  }
-  hipLaunchKernelGGL(dense_mb_kernel, dim3(1), dim3(NT), lds, stream, a);
-  return hipGetLastError();
+  a.P = dense_mb_plan(a.L, a.nl, a.D, a.y != nullptr);
+  return launch(dense_mb_kernel, 1, sizeof(float) * (size_t)a.P.lds_floats, stream, a);
 }
 
 hipError_t dense_mb_fleet_launch(DenseMBArgs a, const DenseMBFleetModel* models, const int32_t* sched, int M,
                                  int64_t stride, hipStream_t stream) {
-  const bool own_targets = a.y != nullptr;
-  if (dense_mb_check(a.L, a.nl, a.D, a.batch, stride, own_targets, a.precision)[0] != 0) return hipErrorInvalidValue;
-  if (M < 1 || a.nsteps < 1 || models == nullptr || sched == nullptr) return hipErrorInvalidValue;
+  if (!launchable(a, stride) || M < 1 || models == nullptr || sched == nullptr) return hipErrorInvalidValue;
   if (a.precision == DMB_BF16) return dense_mb_fleet_launch_bf16(a, models, sched, M, stride, stream);
-  a.P = dense_mb_plan(a.L, a.nl, a.D, own_targets);
-  const size_t lds = sizeof(float) * (size_t)a.P.lds_floats;
-  if (lds > 65536) {
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(dense_mb_fleet_kernel),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-  }
-  hipLaunchKernelGGL(dense_mb_fleet_kernel, dim3(M), dim3(NT), lds, stream, a, models, sched, stride);
-  return hipGetLastError();
+  a.P = dense_mb_plan(a.L, a.nl, a.D, a.y != nullptr);
+  return launch(dense_mb_fleet_kernel, M, sizeof(float) * (size_t)a.P.lds_floats, stream, a, models, sched, stride);
 }
 
 }  // namespace sml

@@ -34,36 +34,31 @@
 // range K pieces read a clamped address and are replaced by zeros).  The kernel synchronises with
 // __syncthreads() only and every loop bound is known at launch.  dense_mb_bf16_fleet_kernel runs M models
 // of one architecture side by side, workgroup b on model sched[b] (sml_dense_fleet.h): the same body
-// (sml_dense_mb_bf16_body.h) on rebased arguments.
+// (sml_dense_mb_bf16_body.h) on rebased arguments.  The limits, the plan and the check are in
+// sml_dense_mb_plan.h; row staging, the loss phase's penalty sum and row merge, and the launch
+// sequence, shared with the fp32 kernel, in sml_dense_mb_dev.h.
 #include "sml_common.h"
 #include "sml_ops.h"
 
 #include "sml_adam.h"
 #include "sml_dense_fleet.h"
+#include "sml_dense_mb_dev.h"
 
 namespace sml {
 namespace {
 
-constexpr int NT = DMB_NT, CH = DMB_CHUNK, NW = NT / 64, SLOTS = DMB_TILES_BF16 / NW;
-constexpr int STAT_SQ = 0, STAT_OK = CH, STAT_PEN = 2 * CH, STAT_TOT = 3 * CH;   // floats from lstat
+using namespace dmb;
+constexpr int NW = NT / 64, SLOTS = DMB_TILES_BF16 / NW;
 static_assert(CH == 32 && NW * SLOTS == DMB_TILES_BF16, "one MFMA K step per chunk; whole tiles per wave");
 
 typedef unsigned char lds_t;
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 __device__ __forceinline__ float* fptr(lds_t* S, int off) { return reinterpret_cast<float*>(S + off); }
-__device__ __forceinline__ f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
-__device__ __forceinline__ void st4(float* p, f32x4 v) { *reinterpret_cast<f32x4*>(p) = v; }
 __device__ __forceinline__ unsigned short to_bf16(float v) { return (unsigned short)(pack2(v, 0.0f) & 0xffffu); }
 
 __device__ __forceinline__ f32x4 mma(s16x8 a, s16x8 b, f32x4 c) {
   return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
-
-// d(l1 * |h| + l2 * h^2) / dh, divided by the step's rows as Keras does
-__device__ __forceinline__ float pen_grad(float l1, float l2, float h, float inv_rows) {
-  const float sg = h > 0.0f ? 1.0f : h < 0.0f ? -1.0f : 0.0f;
-  return (l1 * sg + 2.0f * l2 * h) * inv_rows;
 }
 
 // MFMA operand read by rows: lane (c, g) gets elements k0 + 8g .. + 7 of row row0 + c of a bf16
@@ -139,40 +134,6 @@ __device__ __forceinline__ void bwd_layer(lds_t* S, const DenseMBLayerPlanBF16& 
   }
 }
 
-// rows of one chunk on their way from global memory to LDS: row tid / LPR, columns tid % LPR + LPR e
-constexpr int LPR = NT / CH;            // lanes per row in the staging and loss phases
-constexpr int SE = DMB_MAXW / LPR;      // elements per lane of a row
-static_assert(LPR * CH == NT && LPR <= 32 && (LPR & (LPR - 1)) == 0 && SE * LPR == DMB_MAXW, "row phases: lanes per row");
-struct Stage {
-  float x[SE], y[SE];
-};
-
-template <typename Run>
-__device__ __forceinline__ void stage_load(const DenseMBArgs& a, const Run& run, int O, int s, int k, int steps, Stage& st) {
-  const int r = threadIdx.x / LPR, q = threadIdx.x % LPR;
-  int rows = 0;
-  int64_t pos = 0;
-  if (s < steps) {
-    const int64_t base = run.row0 + (int64_t)s * a.batch;
-    const int64_t left = run.n - base;
-    const int rows_s = left < a.batch ? (int)left : a.batch;
-    rows = rows_s - k * CH < CH ? rows_s - k * CH : CH;
-    pos = base + k * CH + r;
-  }
-  const bool rv = r < rows;
-  int64_t src = 0;
-  if (rv) {
-    src = run.order ? (int64_t)run.order[pos] : pos;
-    src = src < 0 ? 0 : src >= run.n ? run.n - 1 : src;
-  }
-#pragma unroll
-  for (int e = 0; e < SE; ++e) {
-    const int c = q + LPR * e;
-    st.x[e] = (rv && c < a.D) ? run.x[src * a.ldx + c] : 0.0f;
-    st.y[e] = (run.y != nullptr && rv && c < O) ? run.y[src * a.ldy + c] : 0.0f;
-  }
-}
-
 template <typename Run>
 __device__ __forceinline__ void stage_store(lds_t* S, const Run& run, const DenseMBPlanBF16& P, int op, const Stage& st) {
   const int r = threadIdx.x / LPR, q = threadIdx.x % LPR;
@@ -196,19 +157,7 @@ __device__ __forceinline__ void loss_phase(lds_t* S, const DenseMBLayer* sL, con
                                            int ys, int lstat, int rows, float inv_n, float inv_rows) {
   const int r = threadIdx.x / LPR, q = threadIdx.x % LPR;
   const bool rv = r < rows;
-  float pen = 0.0f;
-  for (int l = 0; l < nl; ++l) {
-    const float l1 = sL[l].l1, l2 = sL[l].l2;
-    if (l1 == 0.0f && l2 == 0.0f) continue;
-    float s1 = 0.0f, s2 = 0.0f;
-    const float* hr = fptr(S, sP[l].la) + r * sP[l].hs;
-    for (int j = q; j < sL[l].units; j += LPR) {
-      const float h = hr[j];
-      s1 += fabsf(h);
-      s2 = fmaf(h, h, s2);
-    }
-    pen += l1 * s1 + l2 * s2;
-  }
+  const float pen = pen_sum(sL, nl, q, [&](int l) { return fptr(S, sP[l].la) + r * sP[l].hs; });
   const DenseMBLayer& L = sL[nl - 1];
   const DenseMBLayerPlanBF16& P = sP[nl - 1];
   const bool lpen = L.l1 != 0.0f || L.l2 != 0.0f;
@@ -232,21 +181,7 @@ __device__ __forceinline__ void loss_phase(lds_t* S, const DenseMBLayer* sL, con
     yrow[j] = d;
     drow[j] = to_bf16(d);
   }
-#pragma unroll
-  for (int o = LPR / 2; o > 0; o >>= 1) {
-    sq += __shfl_xor(sq, o, 64);
-    pen += __shfl_xor(pen, o, 64);
-    const float oy = __shfl_xor(by, o, 64), ot = __shfl_xor(bt, o, 64);
-    const int oiy = __shfl_xor(iy, o, 64), oit = __shfl_xor(it, o, 64);
-    if (oy > by || (oy == by && oiy < iy)) { by = oy; iy = oiy; }
-    if (ot > bt || (ot == bt && oit < it)) { bt = ot; it = oit; }
-  }
-  if (q == 0) {
-    float* st = fptr(S, lstat);
-    st[STAT_SQ + r] = rv ? sq : 0.0f;
-    st[STAT_OK + r] = (rv && iy == it) ? 1.0f : 0.0f;
-    st[STAT_PEN + r] = rv ? pen : 0.0f;
-  }
+  row_stats(fptr(S, lstat), r, q, rv, sq, pen, by, iy, bt, it);
 }
 
 // the 16x16 tile of a slot of this wave from its table entry (wave-uniform, read once at launch, so
@@ -277,93 +212,22 @@ __global__ __launch_bounds__(NT) void dense_mb_bf16_fleet_kernel(const DenseMBAr
 #include "sml_dense_mb_bf16_body.h"
 }
 
-constexpr int pad16(int n) { return (n + 15) / 16 * 16; }
-
 }  // namespace
 
-DenseMBPlanBF16 dense_mb_plan_bf16(const DenseMBLayer* L, int nl, int D, bool own_targets) {
-  DenseMBPlanBF16 P{};
-  int off = 0, tiles = 0;
-  P.dp = pad16(D);
-  P.xs = P.dp + 4;
-  P.la0 = off;
-  off += CH * P.xs * 4;
-  P.xbs = P.dp + 8;
-  P.lxb = off;
-  off += CH * P.xbs * 2;
-  int prev = P.dp;
-  for (int l = 0; l < nl; ++l) {
-    DenseMBLayerPlanBF16& q = P.L[l];
-    q.ip = prev;
-    q.up = pad16(L[l].units);
-    q.ws = q.ip + 8;
-    q.lw = off;
-    off += q.up * q.ws * 2;
-    q.lb = off;
-    off += 4 * q.up * 4;
-    q.tile0 = tiles;
-    tiles += (q.ip >> 4) * (q.up >> 4);
-    prev = q.up;
-  }
-  for (int l = 0; l < nl; ++l) {
-    P.L[l].hs = P.L[l].up + 4;
-    P.L[l].la = off;
-    off += CH * P.L[l].hs * 4;
-  }
-  for (int l = 0; l < nl; ++l) {
-    P.L[l].bs = P.L[l].up + 8;
-    P.L[l].lhb = 0;
-    if (l < nl - 1) {
-      P.L[l].lhb = off;
-      off += CH * P.L[l].bs * 2;
-    }
-  }
-  for (int l = 0; l < nl; ++l) {
-    P.L[l].ld = off;
-    off += CH * P.L[l].bs * 2;
-  }
-  if (own_targets) {
-    P.ys = prev + 4;
-    P.lyt = off;
-    off += CH * P.ys * 4;
-  } else {
-    P.ys = P.xs;
-    P.lyt = P.la0;
-  }
-  P.lstat = off;
-  off += 4 * CH * 4;
-  P.ltile = off;
-  off += DMB_TILES_BF16 * 4;
-  P.ntiles = tiles;
-  P.lds_bytes = off;
-  return P;
-}
-
+// Both are reached through dense_mb_launch / dense_mb_fleet_launch, which have run dense_mb_check.  Its
+// MAX_PARAMS_BF16 limit already keeps ntiles within the DMB_TILES_BF16 the waves can own; the test
+// here is for a caller that comes another way.
 hipError_t dense_mb_launch_bf16(const DenseMBArgs& a, hipStream_t stream) {
   const DenseMBPlanBF16 P = dense_mb_plan_bf16(a.L, a.nl, a.D, a.y != nullptr);
   if (P.ntiles > DMB_TILES_BF16) return hipErrorInvalidValue;
-  const size_t lds = (size_t)P.lds_bytes;
-  if (lds > 65536) {
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(dense_mb_bf16_kernel),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-  }
-  hipLaunchKernelGGL(dense_mb_bf16_kernel, dim3(1), dim3(NT), lds, stream, a, P);
-  return hipGetLastError();
+  return launch(dense_mb_bf16_kernel, 1, (size_t)P.lds_bytes, stream, a, P);
 }
 
 hipError_t dense_mb_fleet_launch_bf16(const DenseMBArgs& a, const DenseMBFleetModel* models, const int32_t* sched, int M,
                                       int64_t stride, hipStream_t stream) {
   const DenseMBPlanBF16 P = dense_mb_plan_bf16(a.L, a.nl, a.D, a.y != nullptr);
   if (P.ntiles > DMB_TILES_BF16 || M < 1) return hipErrorInvalidValue;
-  const size_t lds = (size_t)P.lds_bytes;
-  if (lds > 65536) {
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(dense_mb_bf16_fleet_kernel),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-  }
-  hipLaunchKernelGGL(dense_mb_bf16_fleet_kernel, dim3(M), dim3(NT), lds, stream, a, P, models, sched, stride);
-  return hipGetLastError();
+  return launch(dense_mb_bf16_fleet_kernel, M, (size_t)P.lds_bytes, stream, a, P, models, sched, stride);
 }
 
 }  // namespace sml

@@ -1142,6 +1142,60 @@ std::string dense_mb_check(const std::vector<std::vector<double>>& table, int64_
                              own_targets, (int)std::min<int64_t>(std::max<int64_t>(precision, -1), 2));
 }
 
+// How the messages of dense_mb_train and of dense_mb_train_fleet differ: the binding's name, how the row
+// count is written, and what order has to be.
+struct DenseMBWords {
+  const char* who;
+  const char* n;
+  const char* order_is;
+};
+
+// What the two bindings share, in two parts.  The rows: the check of the table against nflat floats of
+// parameters, the table into a.L, the checks of x, y and order against it, and the fields that come
+// from them.  n / row0 / nsteps / lr / out are the caller's.
+static sml::DenseMBArgs dense_mb_rows(const DenseMBWords& w, const std::vector<std::vector<double>>& table, int64_t nflat,
+                                      const at::Tensor& x, const c10::optional<at::Tensor>& y,
+                                      const c10::optional<at::Tensor>& order, int64_t batch, int64_t precision) {
+  sml::DenseMBArgs a{};
+  const std::string why = dense_mb_check(table, batch, nflat, y.has_value(), precision);
+  TORCH_CHECK(why.empty(), w.who, ": ", why);
+  a.nl = dense_mb_table(table, a.L);
+  a.D = a.L[0].in;
+  const int O = a.L[a.nl - 1].units;
+  TORCH_CHECK(x.dim() == 2 && x.size(1) == a.D && (x.size(1) == 1 || x.stride(1) == 1), "x must be [", w.n, ", ", a.D,
+              "] rows with contiguous features");
+  const int64_t rows = x.size(0);
+  if (y.has_value()) {
+    check_dev(*y, "y", at::kFloat);
+    TORCH_CHECK(y->dim() == 2 && y->size(0) == rows && y->size(1) == O && (y->size(1) == 1 || y->stride(1) == 1),
+                "y must be [", w.n, ", ", O, "] rows with contiguous features");
+  }
+  if (order.has_value()) {
+    TORCH_CHECK(order->is_cuda() && order->scalar_type() == at::kInt && order->is_contiguous() && order->numel() == rows,
+                "order must be a device int32 ", w.order_is);
+  }
+  a.x = x.data_ptr<float>();
+  a.ldx = x.stride(0);
+  a.y = y.has_value() ? y->data_ptr<float>() : nullptr;
+  a.ldy = y.has_value() ? y->stride(0) : 0;
+  a.order = order.has_value() ? order->data_ptr<int32_t>() : nullptr;
+  a.batch = (int)batch;
+  a.precision = (int)precision;
+  return a;
+}
+
+// The state: the optimiser's tensors (checked by the caller) and Adam's constants.
+static void dense_mb_state(sml::DenseMBArgs& a, const at::Tensor& flat, const at::Tensor& m, const at::Tensor& v,
+                           const at::Tensor& iter, double beta1, double beta2, double eps) {
+  a.flat = flat.data_ptr<float>();
+  a.m = m.data_ptr<float>();
+  a.v = v.data_ptr<float>();
+  a.iter = iter.data_ptr<int64_t>();
+  a.beta1 = (float)beta1;
+  a.beta2 = (float)beta2;
+  a.eps = (float)eps;
+}
+
 // nsteps consecutive Keras steps of a Dense stack in one launch (dense_minibatch.hip); flat / m / v /
 // iter are updated in place; returns [nsteps, 2] = (mean loss incl. penalties, rows with matching argmax).
 at::Tensor dense_mb_train(const at::Tensor& flat, const at::Tensor& m, const at::Tensor& v, const at::Tensor& iter,
@@ -1156,46 +1210,18 @@ at::Tensor dense_mb_train(const at::Tensor& flat, const at::Tensor& m, const at:
   TORCH_CHECK(iter.is_cuda() && iter.scalar_type() == at::kLong && iter.numel() == 1, "iter must be a device int64[1]");
   TORCH_CHECK(flat.is_contiguous() && m.is_contiguous() && v.is_contiguous() && m.numel() == flat.numel() &&
                   v.numel() == flat.numel(), "flat / m / v must be contiguous and of one size");
-  const std::string why = dense_mb_check(table, batch, flat.numel(), y.has_value(), precision);
-  TORCH_CHECK(why.empty(), "dense_mb_train: ", why);
-  sml::DenseMBArgs a{};
-  a.nl = dense_mb_table(table, a.L);
-  a.D = a.L[0].in;
-  const int O = a.L[a.nl - 1].units;
-  TORCH_CHECK(x.dim() == 2 && x.size(1) == a.D && (x.size(1) == 1 || x.stride(1) == 1), "x must be [n, ", a.D,
-              "] rows with contiguous features");
+  sml::DenseMBArgs a = dense_mb_rows({"dense_mb_train", "n", "permutation of the n samples"}, table, flat.numel(), x, y,
+                                     order, batch, precision);
+  dense_mb_state(a, flat, m, v, iter, beta1, beta2, eps);
   const int64_t n = x.size(0);
-  if (y.has_value()) {
-    check_dev(*y, "y", at::kFloat);
-    TORCH_CHECK(y->dim() == 2 && y->size(0) == n && y->size(1) == O && (y->size(1) == 1 || y->stride(1) == 1),
-                "y must be [n, ", O, "] rows with contiguous features");
-  }
-  if (order.has_value()) {
-    TORCH_CHECK(order->is_cuda() && order->scalar_type() == at::kInt && order->is_contiguous() && order->numel() == n,
-                "order must be a device int32 permutation of the n samples");
-  }
   TORCH_CHECK(nsteps >= 1 && nsteps < (1 << 30) && row0 >= 0 && row0 < n, "bad nsteps / row0");
   c10::hip::HIPGuard guard(x.device().index());
   auto out = at::zeros({nsteps, 2}, flat.options());
-  a.flat = flat.data_ptr<float>();
-  a.m = m.data_ptr<float>();
-  a.v = v.data_ptr<float>();
-  a.iter = iter.data_ptr<int64_t>();
-  a.x = x.data_ptr<float>();
-  a.ldx = x.stride(0);
-  a.y = y.has_value() ? y->data_ptr<float>() : nullptr;
-  a.ldy = y.has_value() ? y->stride(0) : 0;
-  a.order = order.has_value() ? order->data_ptr<int32_t>() : nullptr;
   a.n = n;
   a.row0 = row0;
-  a.batch = (int)batch;
   a.nsteps = (int)nsteps;
   a.lr = (float)lr;
-  a.beta1 = (float)beta1;
-  a.beta2 = (float)beta2;
-  a.eps = (float)eps;
   a.out = out.data_ptr<float>();
-  a.precision = (int)precision;
   SML_CHECK_HIP(sml::dense_mb_launch(a, cur_stream(x)));
   return out;
 }
@@ -1222,25 +1248,11 @@ at::Tensor dense_mb_train_fleet(const at::Tensor& flat, const at::Tensor& m, con
   TORCH_CHECK(M < (1 << 24), "a fleet of ", M, " models: the limit is ", (1 << 24) - 1);
   TORCH_CHECK(iter.is_cuda() && iter.scalar_type() == at::kLong && iter.is_contiguous() && iter.numel() == M,
               "iter must be a device int64[", M, "]");
-  // stride >= nflat: every parameter offset of the table lies inside a model's segment
-  const std::string why = dense_mb_check(table, batch, stride, y.has_value(), precision);
-  TORCH_CHECK(why.empty(), "dense_mb_train_fleet: ", why);
-  sml::DenseMBArgs a{};
-  a.nl = dense_mb_table(table, a.L);
-  a.D = a.L[0].in;
-  const int O = a.L[a.nl - 1].units;
-  TORCH_CHECK(x.dim() == 2 && x.size(1) == a.D && (x.size(1) == 1 || x.stride(1) == 1), "x must be [N, ", a.D,
-              "] rows with contiguous features");
+  // the table is checked against stride floats: every parameter offset then lies inside a model's segment
+  sml::DenseMBArgs a = dense_mb_rows({"dense_mb_train_fleet", "N", "[N] of indices local to each model's rows"}, table,
+                                     stride, x, y, order, batch, precision);
+  dense_mb_state(a, flat, m, v, iter, beta1, beta2, eps);
   const int64_t N = x.size(0);
-  if (y.has_value()) {
-    check_dev(*y, "y", at::kFloat);
-    TORCH_CHECK(y->dim() == 2 && y->size(0) == N && y->size(1) == O && (y->size(1) == 1 || y->stride(1) == 1),
-                "y must be [N, ", O, "] rows with contiguous features");
-  }
-  if (order.has_value()) {
-    TORCH_CHECK(order->is_cuda() && order->scalar_type() == at::kInt && order->is_contiguous() && order->numel() == N,
-                "order must be a device int32 [N] of indices local to each model's rows");
-  }
   TORCH_CHECK(!models.is_cuda() && models.scalar_type() == at::kLong && models.is_contiguous() && models.dim() == 2 &&
                   models.size(0) == M && models.size(1) == 4,
               "models must be a host int64 [", M, ", 4] tensor of descriptors");
@@ -1269,22 +1281,8 @@ at::Tensor dense_mb_train_fleet(const at::Tensor& flat, const at::Tensor& m, con
   // the kernels load no vectors from global memory except the descriptors (32 bytes each)
   TORCH_CHECK(reinterpret_cast<uintptr_t>(models_d.data_ptr<int64_t>()) % 16 == 0, "descriptors are not 16-byte aligned");
   auto out = at::zeros({M, S, 2}, flat.options());
-  a.flat = flat.data_ptr<float>();
-  a.m = m.data_ptr<float>();
-  a.v = v.data_ptr<float>();
-  a.iter = iter.data_ptr<int64_t>();
-  a.x = x.data_ptr<float>();
-  a.ldx = x.stride(0);
-  a.y = y.has_value() ? y->data_ptr<float>() : nullptr;
-  a.ldy = y.has_value() ? y->stride(0) : 0;
-  a.order = order.has_value() ? order->data_ptr<int32_t>() : nullptr;
-  a.batch = (int)batch;
   a.nsteps = (int)S;
-  a.beta1 = (float)beta1;
-  a.beta2 = (float)beta2;
-  a.eps = (float)eps;
   a.out = out.data_ptr<float>();
-  a.precision = (int)precision;
   SML_CHECK_HIP(sml::dense_mb_fleet_launch(a, reinterpret_cast<const sml::DenseMBFleetModel*>(models_d.data_ptr<int64_t>()),
                                            sched_d.data_ptr<int32_t>(), (int)M, stride, cur_stream(x)));
   return out;

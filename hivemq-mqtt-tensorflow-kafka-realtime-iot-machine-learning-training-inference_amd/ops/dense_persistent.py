@@ -10,8 +10,10 @@ one bf16 weight image in LDS; its limits are its own (``MAX_PARAMS_BF16``).  The
 per-step ``[loss, correct]`` come back as a device tensor, as ``ops.lstm_persistent`` does for
 the reference LSTM stack.
 
-``supports`` needs no device: it mirrors the C++ checks (``dense_mb_check``) and names the limit
-a model exceeds.
+``supports`` needs no device and no built extension: it mirrors the C++ checks and LDS plans
+(``dense_mb_check``, ``dense_mb_plan``, ``dense_mb_plan_bf16`` of ``csrc/include/sml_dense_mb_plan.h``)
+and names the limit a model exceeds.  ``tests/test_dense_mb_plan.py`` holds the two copies together on
+the CPU, through a host program over that header.
 """
 from __future__ import annotations
 
