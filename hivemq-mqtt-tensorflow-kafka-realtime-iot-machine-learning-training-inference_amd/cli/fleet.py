@@ -9,8 +9,9 @@ key with the same Keras-batch semantics, all models at once on one GPU
 
 ``--layers 64,16,64`` trains the Dense stack ``cardata-v3 --layers`` builds (18 in, 18 out, tanh /
 relu alternating, relu last) instead, one persistent workgroup per model (``ops/dense_fleet.py``),
-on rows normalised once on the host; every ``.h5`` is one ``serve --model dense`` accepts and
-``index.json`` also records ``layers``, ``engine`` and ``precision``.
+on rows normalised once on the host; every ``.h5`` is one ``serve --model dense`` accepts,
+``index.json`` also records ``layers``, ``engine`` and ``precision``, and the whole directory is what
+``serve --model dense-fleet <dir>`` scores the live stream with, every car by its own model.
 
   fleet <csv|synthetic> [--models N] [--epochs E] [--batch 32] [--lr 1e-3] [--out DIR]
         [--layers 64,16,64 [--precision fp32|bf16]]

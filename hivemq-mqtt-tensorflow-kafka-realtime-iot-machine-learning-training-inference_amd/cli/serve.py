@@ -22,7 +22,9 @@ only (cardata-v3.py:46) and writes reconstructions (cardata-v3.py:243-249). Here
 (:class:`streamml.ops.serve.ScoringServer`; ``--model lstm``: the per-car forecaster
 :class:`~streamml.ops.serve.LSTMScoringServer`, car key -> device slot in C++; ``--model dense``:
 :class:`~streamml.ops.serve.DenseScoringServer` for a Dense autoencoder of any depth, on both
-the chunked and the low-latency path), no launch
+the chunked and the low-latency path; ``--model dense-fleet <dir>``: the directory ``fleet --layers``
+wrote, every car scored by its own model on one resident
+:class:`~streamml.ops.serve.DenseFleetScoringServer`, car key -> model index from ``index.json``), no launch
 per event -> the same result records formatted in C++ -> one produce per fetch -> commit.
 
 Replica identity comes from ``--replica-index/--replicas``, else torchrun's
@@ -96,11 +98,16 @@ def _flags(p) -> None:
                    help="--low-latency: CPUs for the loop thread, e.g. '4' or '4-7,12', or 'auto' (one core of "
                         "an L3 domain, a different one per replica); a loopback hop across core "
                         "complexes costs microseconds (profiles/r04 SUMMARY §7)")
-    p.add_argument("--model", choices=["autoencoder", "lstm", "dense"], default="autoencoder",
+    p.add_argument("--model", choices=["autoencoder", "lstm", "dense", "dense-fleet"], default="autoencoder",
                    help="lstm: per-car forecaster (look_back events per car on the device, each event "
                         "scored against the car's previous forecast; lstm_serve.hip).  dense: a Dense "
                         "autoencoder of any depth (1..8 layers up to 512 wide, saved from nn.Sequential / "
-                        "nn.Model) on the persistent scorer of dense_serve.hip")
+                        "nn.Model) on the persistent scorer of dense_serve.hip.  dense-fleet: <model-file> is "
+                        "the output directory of fleet --layers; every car is scored by the model that "
+                        "index.json gives its key, all on one resident scorer (dense_serve_fleet.hip)")
+    p.add_argument("--fallback-model", default=None, metavar="NAME",
+                   help="--model dense-fleet: score cars that index.json does not name with this member "
+                        "(default: drop them, counted as keys_dropped)")
     p.add_argument("--max-keys", type=int, default=200_000, help="--model lstm: car keys held on the device")
     p.add_argument("--lanes", type=int, default=1,
                    help="--model lstm: resident workgroups of the forecaster; car key k is served by lane "
@@ -155,6 +162,47 @@ def _require_dense_servable(model) -> None:
         raise SystemExit(f"--model dense: the cardata normaliser needs 18 input features, the model has {features}")
 
 
+class _FleetDir:
+    """``--model dense-fleet``: the members of a ``fleet --layers`` directory, loaded on the CPU and
+    checked, and the car key -> model index table; stands where the other paths hold a model."""
+
+    name = "dense-fleet"
+
+    def __init__(self, path: str, device, fallback=None):
+        import torch
+
+        from ..ops.serve import DenseFleetScoringServer
+        if not os.path.isdir(path):
+            raise SystemExit(f"--model dense-fleet: {path} is not a directory (expected the output of fleet --layers)")
+        try:
+            self.models, self.names, self.key_to_model = DenseFleetScoringServer.load_dir(path)
+        except ValueError as e:
+            raise SystemExit(f"--model dense-fleet: {e}")
+        features = int(self.models[0]._input_shape()[0])
+        if features != 18:
+            raise SystemExit(f"--model dense-fleet: the cardata normaliser needs 18 input features, the models "
+                             f"have {features}")
+        self.fallback = -1
+        if fallback is not None:
+            if fallback not in self.names:
+                raise SystemExit(f"--fallback-model {fallback}: index.json names no such model")
+            self.fallback = self.names.index(fallback)
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise SystemExit("--model dense-fleet serving needs a ROCm device (the persistent scorer)")
+
+    def server(self, threshold: float, slots: int = 4096):
+        from ..ops.serve import DenseFleetScoringServer
+        return DenseFleetScoringServer(self.models, thresholds=threshold, normalizer="cardata", slots=slots,
+                                       device=self.device)
+
+    def indices(self, keys):
+        """(model index per record, -1 for a car no member owns and no fallback takes)."""
+        table, fb = self.key_to_model, self.fallback
+        return np.fromiter((table.get(k.decode("utf-8", "replace") if isinstance(k, bytes) else str(k), fb)
+                            if k is not None else -1 for k in keys), np.int64, len(keys))
+
+
 def _serve_low_latency(ns, servers, cfg, model, mine, result_parts, summary, rank: int = 0,
                        hash_ranges=None) -> int:
     """One C++ loop per replica over the resident scorer: the autoencoder's, or -- ``--model
@@ -170,8 +218,12 @@ def _serve_low_latency(ns, servers, cfg, model, mine, result_parts, summary, ran
         raise SystemExit("--low-latency needs a ROCm device (the persistent scorer)")
     if ns.model == "lstm":
         _require_servable(model, ns.lanes)
+    key_table, unknown = None, -1
     if ns.model == "lstm":
         scorer = LSTMScoringServer(model, nkeys=ns.max_keys, threshold=ns.threshold, lanes=ns.lanes)
+    elif ns.model == "dense-fleet":
+        scorer = model.server(ns.threshold)
+        key_table, unknown = model.key_to_model, model.fallback
     elif ns.model == "dense":
         scorer = DenseScoringServer(model, threshold=ns.threshold, normalizer="cardata")
     else:
@@ -186,7 +238,7 @@ def _serve_low_latency(ns, servers, cfg, model, mine, result_parts, summary, ran
                                 starts=starts, result_partitions=[p % result_parts for p in mine],
                                 emit_recon=ns.emit == "both", config=cfg, max_batch=min(ns.max_batch, 4096),
                                 max_wait_ms=ns.max_wait_ms, spin_us=ns.spin_us, source_format=ns.source_format,
-                                hash_ranges=hash_ranges)
+                                hash_ranges=hash_ranges, key_table=key_table, unknown_key_id=unknown)
         mask = os.sched_getaffinity(0)
         cpus = resolve_cpus(ns.cpus, slot=rank)
         if cpus:
@@ -201,6 +253,8 @@ def _serve_low_latency(ns, servers, cfg, model, mine, result_parts, summary, ran
         summary.update(model="lstm", keys=st["keys"])
     elif ns.model == "dense":
         summary.update(model="dense")
+    elif ns.model == "dense-fleet":
+        summary.update(model="dense-fleet", models=len(model.names), kernel="fleet")
     summary.update(events=st["events"], anomalies=st["anomalies"], skipped=st["skipped"], foreign=st["foreign"],
                    keys_dropped=st["keys_dropped"],
                    events_per_s=st["events"] / st["wall_s"] if st["wall_s"] > 0 else 0.0, low_latency=True,
@@ -228,14 +282,21 @@ def main(argv: Sequence[str]) -> int:
         import torch
         device = f"cuda:{int(os.environ.get('LOCAL_RANK', '0'))}" if torch.cuda.is_available() else "cpu"
 
+    if ns.fallback_model is not None and ns.model != "dense-fleet":
+        raise SystemExit("--fallback-model goes with --model dense-fleet")
     path = common.model_path(ns.workdir, ns.model_file)
-    if not os.path.exists(path):
+    if ns.model == "dense-fleet":
+        if not os.path.isdir(path) and os.path.isdir(ns.model_file):
+            path = ns.model_file
+    elif not os.path.exists(path):
         if ns.model == "lstm":
             from ..utils.model_store import lstm_store
             lstm_store(ns.store).download(ns.model_file, path)
         else:
             autoencoder_store(ns.project, ns.store).download("/" + ns.model_file, path)
-    if ns.model == "lstm":
+    if ns.model == "dense-fleet":
+        model = _FleetDir(path, device, ns.fallback_model)
+    elif ns.model == "lstm":
         from ..models.lstm import LSTMPredictor
         model = LSTMPredictor.load(path, device=device)
     elif ns.model == "dense":
@@ -277,7 +338,10 @@ def main(argv: Sequence[str]) -> int:
     if ns.low_latency:
         return _serve_low_latency(ns, servers, cfg, model, mine, result_parts, summary, rank,
                                   [(lo, hi) for _, lo, hi in shares])
-    forecaster, key_ids, dense_srv = None, {}, None
+    forecaster, key_ids, dense_srv, fleet_srv = None, {}, None, None
+    if ns.model == "dense-fleet":
+        fleet_srv = model.server(ns.threshold, slots=max(64, min(ns.max_batch, 4096)))
+        summary["keys_dropped"] = 0
     if ns.model == "dense":
         from ..ops.serve import DenseScoringServer
         dense_srv = DenseScoringServer(model, threshold=ns.threshold, normalizer="cardata",
@@ -308,9 +372,22 @@ def main(argv: Sequence[str]) -> int:
             chunk = chunk.select(ok)
         if len(chunk) == 0:
             continue
+        if fleet_srv is not None:   # car key -> its model; cars no member owns are dropped, counted
+            midx = model.indices(chunk.keys or [None] * len(chunk))
+            known = midx >= 0
+            if not known.all():
+                summary["keys_dropped"] += int((~known).sum())
+                chunk, midx = chunk.select(known), midx[known]
+            if len(chunk) == 0:
+                continue
         t_batch = time.perf_counter()
         recon = None
-        if forecaster is not None:
+        if fleet_srv is not None:
+            if ns.emit == "both":
+                scores, flags, recon = fleet_srv.infer(chunk.x, midx)
+            else:
+                scores, flags = fleet_srv.score(chunk.x, midx)
+        elif forecaster is not None:
             # car key -> device slot (first come, first served; the table holds --max-keys cars)
             ids = np.empty(len(chunk), np.int64)
             for i, k in enumerate(chunk.keys or [None] * len(chunk)):
@@ -361,6 +438,9 @@ def main(argv: Sequence[str]) -> int:
     if dense_srv is not None:
         summary.update(model="dense", kernel=dense_srv.kernel)
         dense_srv.close()
+    if fleet_srv is not None:
+        summary.update(model="dense-fleet", models=fleet_srv.n_models, kernel=fleet_srv.kernel)
+        fleet_srv.close()
     wall = time.perf_counter() - t0
     summary["events_per_s"] = summary["events"] / wall if wall > 0 else 0.0
     print(json.dumps(summary), flush=True)

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "sml_dense_fleet_serve.h"
 #include "sml_dense_mb_plan.h"
 
 namespace sml {
@@ -334,27 +335,8 @@ void lstm_serve_wide_image(const float* w, int K, int u, int Kp, int up, uint16_
 hipError_t lstm_serve_wide_launch(const LstmServeArgs& args, hipStream_t stream);
 
 // ---- persistent per-event scorer for Dense stacks of any depth (dense_serve.hip) ----
-// Same rings, framing and result words as ae_serve: 1..DSV_MAXLAYERS Dense layers, every width
-// 1..DSV_MAXW, rows of 1..32 features, the last layer one unit per feature.  fp32 throughout.
-// One resident workgroup scores up to DSV_EB events per pass; an event's result bits do not
-// depend on how the ring batched it.
-enum : int {
-  DSV_MAXW = 512,             // units / inputs of a layer
-  DSV_MAXLAYERS = 8,
-  DSV_EB = 8,                 // events per pass
-  DSV_NT = 1024,              // threads of the workgroup
-  DSV_TILE = 32,              // output widths are zero-padded to this, input widths to 4
-  DSV_MAXKS = 16,             // slices of a layer's reduction
-  // bytes of weight image that fit the CU's 160 KiB of LDS beside the activation and
-  // partial-sum buffers (64 KiB) and the kernel's small static arrays: at or below this
-  // the image is copied to LDS at launch ("lds"), above it every pass streams it ("stream")
-  DSV_LDS_IMAGE_BYTES = 92 * 1024
-};
-struct DenseServeLayer {
-  int in, out;         // input width, units
-  int act;             // ACT_* code
-  int w_off, b_off;    // float offsets of the layer's weight image and padded bias in the image
-};
+// The limits, DenseServeLayer and the image's geometry are in sml_dense_fleet_serve.h (plain C++,
+// shared with the fleet scorer and its host-side check).
 struct DenseServeArgs {
   ServeCtl* ctl;
   const ServeReq* req;
@@ -371,25 +353,16 @@ struct DenseServeArgs {
   uint64_t idle_ticks;
   uint64_t* stats;     // host-mapped: {passes << 32 | events}, cumulative, stored after each pass
 };
-constexpr int dense_serve_kp(int in) { return (in + 3) / 4 * 4; }
-constexpr int dense_serve_np(int out) { return (out + DSV_TILE - 1) / DSV_TILE * DSV_TILE; }
-// slices of a layer's reduction: a power of two fixed by the layer's shape alone -- the largest
-// with Np * KS <= DSV_NT threads, at least one 4-row group per slice and KS <= DSV_MAXKS
-constexpr int dense_serve_k_slices(int in, int out) {
-  int ks = 1;
-  while (dense_serve_np(out) * ks * 2 <= DSV_NT && ks * 2 <= dense_serve_kp(in) / 4 && ks * 2 <= DSV_MAXKS) ks *= 2;
-  return ks;
-}
-// floats of one layer in the image: float4 img[Kp / 4][Np] (img[g][o] = W[4g .. 4g + 3][o]), then bias[Np]
-constexpr int dense_serve_layer_floats(int in, int out) {
-  return dense_serve_kp(in) * dense_serve_np(out) + dense_serve_np(out);
-}
 // empty if the kernel can serve the stack (D features, nl layers, offsets inside an image of
 // img_floats floats), else the limit it exceeds
 const char* dense_serve_check(const DenseServeLayer* L, int nl, int D, int64_t img_floats);
 // the whole image goes to LDS: a pure function of the layer table and DSV_LDS_IMAGE_BYTES
 bool dense_serve_in_lds(const DenseServeLayer* L, int nl);
 hipError_t dense_serve_launch(const DenseServeArgs& args, hipStream_t stream);
+
+// ---- persistent per-event scorer for a fleet of Dense stacks (dense_serve_fleet.hip) ----
+// DenseFleetServeArgs and dense_fleet_serve_check: sml_dense_fleet_serve.h
+hipError_t dense_fleet_serve_launch(const DenseFleetServeArgs& args, hipStream_t stream);
 
 // ---- persistent small-batch trainer for Dense stacks of any depth (dense_minibatch.hip) ----
 // One workgroup runs nsteps sequential Keras steps (forward, MSE + activity penalties, categorical

@@ -460,7 +460,7 @@ PYBIND11_MODULE(_io, m) {
                        int32_t max_bytes, int32_t max_wait_ms, double commit_interval_s, bool record_latency,
                        uintptr_t api, int spin_us, std::vector<std::pair<std::string, int>> json_columns,
                        const std::string& json_stamp, std::vector<std::pair<uint64_t, uint64_t>> hash_ranges,
-                       int offset_reset) {
+                       int offset_reset, py::object key_table, int64_t unknown_key_id) {
              kafka::ClientConfig c;
              c.client_id = client_id;
              c.sasl_mechanism = mech;
@@ -487,6 +487,15 @@ PYBIND11_MODULE(_io, m) {
              lc.json_stamp = json_stamp;
              lc.hash_ranges = std::move(hash_ranges);
              lc.offset_reset = offset_reset;
+             if (!key_table.is_none()) {   // {key bytes -> id}
+               lc.has_key_table = true;
+               lc.unknown_key_id = unknown_key_id;
+               for (auto item : key_table.cast<py::dict>()) {
+                 const int64_t id = item.second.cast<int64_t>();
+                 if (id < 0 || id > 0xffffffffLL) throw std::invalid_argument("scoreloop: key table id outside uint32");
+                 lc.key_table.emplace_back(item.first.cast<py::bytes>().cast<std::string>(), (uint32_t)id);
+               }
+             }
              return new serve::ScoreLoop(bootstrap, c, fields_from_py(fields), lc,
                                          reinterpret_cast<const SmlScorerApi*>(api));
            }),
@@ -497,7 +506,8 @@ PYBIND11_MODULE(_io, m) {
            py::arg("max_batch"), py::arg("max_bytes"), py::arg("max_wait_ms"), py::arg("commit_interval_s"),
            py::arg("record_latency"), py::arg("scorer_api"), py::arg("spin_us") = 0,
            py::arg("json_columns") = std::vector<std::pair<std::string, int>>{}, py::arg("json_stamp") = "",
-           py::arg("hash_ranges") = std::vector<std::pair<uint64_t, uint64_t>>{}, py::arg("offset_reset") = 0)
+           py::arg("hash_ranges") = std::vector<std::pair<uint64_t, uint64_t>>{}, py::arg("offset_reset") = 0,
+           py::arg("key_table") = py::none(), py::arg("unknown_key_id") = -1)
       .def("run",
            [](serve::ScoreLoop& l, int64_t max_events, double idle_timeout_s) {
              serve::LoopStats st;

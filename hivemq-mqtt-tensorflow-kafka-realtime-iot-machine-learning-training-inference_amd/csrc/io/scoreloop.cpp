@@ -65,6 +65,14 @@ ScoreLoop::ScoreLoop(std::string bootstrap, kafka::ClientConfig ccfg, std::vecto
   if (!cfg_.hash_ranges.empty() && cfg_.hash_ranges.size() != cfg_.partitions.size())
     throw std::invalid_argument("scoreloop: one hash range per owned partition");
   if (cfg_.max_batch < 1) throw std::invalid_argument("scoreloop: max_batch >= 1");
+  if (cfg_.has_key_table) {
+    if (api_->nkeys <= 0) throw std::invalid_argument("scoreloop: a key table needs a keyed scorer");
+    if (cfg_.unknown_key_id >= api_->nkeys) throw std::invalid_argument("scoreloop: unknown_key_id outside [0, nkeys)");
+    for (const auto& kv : cfg_.key_table) {
+      if ((int64_t)kv.second >= api_->nkeys) throw std::invalid_argument("scoreloop: key table id outside [0, nkeys)");
+      key_ids_[kv.first] = kv.second;
+    }
+  }
   pos_ = cfg_.starts;
 }
 
@@ -225,12 +233,21 @@ LoopStats ScoreLoop::run(int64_t max_events, double idle_timeout_s) {
           }
           std::string key(reinterpret_cast<const char*>(kv.first), (size_t)kv.second);
           auto it = key_ids_.find(key);
-          if (it == key_ids_.end()) {
+          uint32_t kid = 0;
+          if (it != key_ids_.end()) {
+            kid = it->second;
+          } else if (cfg_.has_key_table) {   // preset ids: an unknown key goes to the fallback id or is dropped
+            if (cfg_.unknown_key_id < 0) {
+              ++st.keys_dropped;
+              continue;
+            }
+            kid = (uint32_t)cfg_.unknown_key_id;
+          } else {
             if ((int64_t)key_ids_.size() >= api_->nkeys) {
               ++st.keys_dropped;
               continue;
             }
-            it = key_ids_.emplace(std::move(key), (uint32_t)key_ids_.size()).first;
+            kid = key_ids_.emplace(std::move(key), (uint32_t)key_ids_.size()).first->second;
             st.keys = key_ids_.size();
           }
           if (w != i) {
@@ -240,7 +257,7 @@ LoopStats ScoreLoop::run(int64_t max_events, double idle_timeout_s) {
             stamps[(size_t)w] = stamps[(size_t)i];
             src[(size_t)w] = src[(size_t)i];
           }
-          kids[(size_t)w++] = it->second;
+          kids[(size_t)w++] = kid;
         }
         k = w;
       }

@@ -63,6 +63,13 @@ struct LoopConfig {
   // owned partition.  Replicas sharing a partition split its cars this way, each car on
   // exactly one replica, in order.
   std::vector<std::pair<uint64_t, uint64_t>> hash_ranges;
+  // keyed scorers: a preset record key -> id table (a fleet scorer's car key -> model index).  With
+  // one the loop never assigns ids itself: a key outside the table is scored as unknown_key_id, or
+  // -- unknown_key_id < 0 -- skipped and counted (LoopStats::keys_dropped).  Without one
+  // (has_key_table false) ids are given first come, first served.
+  bool has_key_table = false;
+  std::vector<std::pair<std::string, uint32_t>> key_table;
+  int64_t unknown_key_id = -1;
 };
 
 struct LoopStats {
@@ -101,7 +108,8 @@ class ScoreLoop {
   std::unique_ptr<jsonrow::Plan> json_;   // JSON source records
   // keyed scorers: record key -> device slot, first come first served (the device keeps
   // each slot's window); records of keys past the scorer's nkeys slots, and null-keyed
-  // records, are skipped and counted (LoopStats::keys_dropped), never scored into a shared slot
+  // records, are skipped and counted (LoopStats::keys_dropped), never scored into a shared slot.
+  // With LoopConfig::key_table the map is that table and stays as it is.
   std::unordered_map<std::string, uint32_t> key_ids_;
   std::vector<int64_t> pos_;
   std::vector<int64_t> lat_;

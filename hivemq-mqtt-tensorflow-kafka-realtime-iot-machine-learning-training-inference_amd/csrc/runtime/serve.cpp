@@ -180,6 +180,136 @@ uint64_t DenseServe::stats() const {
   return v;
 }
 
+int DenseFleetServe::checked_D(const float* images, int64_t n_models, int64_t stride, int64_t img_floats,
+                               const std::vector<DenseServeLayer>& layers, int D, const std::vector<float>& scale,
+                               const std::vector<float>& shift, const std::vector<float>& thresholds) {
+  if (layers.empty() || layers.size() > (size_t)DSV_MAXLAYERS)
+    throw std::invalid_argument("DenseFleetServe: the stack must have 1..8 Dense layers");
+  const char* why = dense_fleet_serve_check(layers.data(), (int)layers.size(), D, img_floats, stride, n_models);
+  if (why[0]) throw std::invalid_argument(std::string("DenseFleetServe: ") + why);
+  if (!images) throw std::invalid_argument("DenseFleetServe: no images");
+  if ((int64_t)thresholds.size() != n_models) throw std::invalid_argument("DenseFleetServe: one threshold per model");
+  if (!scale.empty() && ((int)scale.size() != D || (int)shift.size() != D))
+    throw std::invalid_argument("DenseFleetServe: scale/shift size");
+  return D;
+}
+
+DenseFleetServe::DenseFleetServe(int device, int nslots, const float* images, int64_t n_models, int64_t stride,
+                                 int64_t img_floats, const std::vector<DenseServeLayer>& layers, int D,
+                                 const std::vector<float>& scale, const std::vector<float>& shift,
+                                 const std::vector<float>& thresholds, double idle_seconds)
+    // request word 31 carries the model index
+    : ServeRing(device, nslots, checked_D(images, n_models, stride, img_floats, layers, D, scale, shift, thresholds),
+                idle_seconds, DSV_FLEET_MAXD) {
+  name_ = "DenseFleetServe";
+  DenseFleetServeArgs& a = args_;
+  a.nslots = nslots_;
+  a.D = D;
+  a.nl = (int)layers.size();
+  for (size_t i = 0; i < layers.size(); ++i) a.L[i] = layers[i];
+  a.img_floats = (int)img_floats;
+  a.stride = (int)stride;
+  a.n_models = (int)n_models;
+  a.idle_ticks = (uint64_t)(idle_seconds * 100e6);   // s_memrealtime runs at 100 MHz
+  ck(hipHostMalloc((void**)&stats_, 128, hipHostMallocMapped | hipHostMallocCoherent), "hipHostMalloc stats");
+  std::memset(stats_, 0, 128);
+  ck(hipHostGetDevicePointer((void**)&a.stats, stats_, 0), "device ptr stats");
+  const size_t nimg = (size_t)n_models * (size_t)stride;
+  ck(hipMalloc((void**)&img_d_, nimg * sizeof(float)), "hipMalloc weight images");
+  ck(hipMemcpy(img_d_, images, nimg * sizeof(float), hipMemcpyHostToDevice), "copy weight images");
+  ck(hipMalloc((void**)&thr_d_, (size_t)n_models * sizeof(float)), "hipMalloc thresholds");
+  ck(hipMemcpy(thr_d_, thresholds.data(), (size_t)n_models * sizeof(float), hipMemcpyHostToDevice),
+     "copy thresholds");
+  if (!scale.empty()) {
+    ck(hipMalloc((void**)&scale_d_, D * sizeof(float)), "hipMalloc scale");
+    ck(hipMalloc((void**)&shift_d_, D * sizeof(float)), "hipMalloc shift");
+    ck(hipMemcpy(scale_d_, scale.data(), D * sizeof(float), hipMemcpyHostToDevice), "copy scale");
+    ck(hipMemcpy(shift_d_, shift.data(), D * sizeof(float), hipMemcpyHostToDevice), "copy shift");
+  }
+  a.ctl = ctl_d_;
+  a.req = req_d_;
+  a.res = res_d_;
+  a.img = img_d_;
+  a.thr = thr_d_;
+  a.scale = scale_d_;
+  a.shift = shift_d_;
+  launch();
+}
+
+DenseFleetServe::~DenseFleetServe() {
+  try {
+    stop();
+  } catch (...) {
+  }
+  if (img_d_) (void)hipFree(img_d_);
+  if (thr_d_) (void)hipFree(thr_d_);
+  if (scale_d_) (void)hipFree(scale_d_);
+  if (shift_d_) (void)hipFree(shift_d_);
+  if (stats_) (void)hipHostFree(stats_);
+}
+
+hipError_t DenseFleetServe::launch_kernel() { return dense_fleet_serve_launch(args_, stream_); }
+
+uint64_t DenseFleetServe::stats() const {
+  // as DenseServe::stats: the word lands a moment after the result words wait() polls
+  const uint32_t want = (uint32_t)complete_[0];
+  const auto t0 = std::chrono::steady_clock::now();
+  uint64_t v = load_acq(stats_);
+  while ((uint32_t)v != want && std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() < 0.5) {
+    cpu_relax();
+    v = load_acq(stats_);
+  }
+  return v;
+}
+
+int64_t DenseFleetServe::first_bad_index(const uint32_t* models, int64_t k) const {
+  const uint32_t M = (uint32_t)args_.n_models;
+  for (int64_t i = 0; i < k; ++i)
+    if (models[i] >= M) return i;
+  return -1;
+}
+
+void DenseFleetServe::infer(const float* rows, const uint32_t* models, int k, float* scores, uint32_t* flags,
+                            float* recon, double timeout_s) {
+  if (k > 0 && !models) throw std::invalid_argument("DenseFleetServe: one model index per row");
+  // the kernel trusts word 31: nothing is published unless every index names a model
+  const int64_t bad = first_bad_index(models, k);
+  if (bad >= 0)
+    throw std::invalid_argument("DenseFleetServe: model index " + std::to_string(models[bad]) + " of row " +
+                                std::to_string(bad) + " is outside [0, " + std::to_string(args_.n_models) + ")");
+  ServeRing::infer(rows, k, scores, flags, recon, timeout_s, models);
+}
+
+void DenseFleetServe::halt() {
+  // the resident kernel reads the images: stop it (flag + drain the stream) as LSTMServe::reset_keys
+  // does, so the copy never queues behind a kernel that only leaves at its idle timeout
+  stop();
+  const auto t0 = std::chrono::steady_clock::now();
+  while (__atomic_load_n(&ctl_->alive, __ATOMIC_ACQUIRE) != 0) {   // stored last by the leaving kernel
+    cpu_relax();
+    if (std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > 10.0)
+      throw std::runtime_error("DenseFleetServe: the resident kernel did not leave");
+  }
+}
+
+void DenseFleetServe::set_image(int64_t i, const float* image) {
+  if (i < 0 || i >= (int64_t)args_.n_models)
+    throw std::invalid_argument("DenseFleetServe: model index " + std::to_string(i) + " is outside [0, " +
+                                std::to_string(args_.n_models) + ")");
+  halt();
+  ck(hipSetDevice(device_), "hipSetDevice");
+  ck(hipMemcpy(img_d_ + (size_t)i * (size_t)args_.stride, image, (size_t)args_.stride * sizeof(float),
+               hipMemcpyHostToDevice),
+     "copy weight image");
+}
+
+void DenseFleetServe::set_images(const float* images) {
+  halt();
+  ck(hipSetDevice(device_), "hipSetDevice");
+  ck(hipMemcpy(img_d_, images, (size_t)args_.n_models * (size_t)args_.stride * sizeof(float), hipMemcpyHostToDevice),
+     "copy weight images");
+}
+
 int LSTMServe::checked_lanes(int device, int lanes, const std::vector<LstmServeLayer>& layers, int D, int T) {
   if (lanes == 1) return lanes;
   if (lanes < 1 || lanes > LSW_MAXLANES)

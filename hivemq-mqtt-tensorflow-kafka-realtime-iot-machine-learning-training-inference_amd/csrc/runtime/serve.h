@@ -154,6 +154,51 @@ class DenseServe : public ServeRing {
   float* shift_d_ = nullptr;
 };
 
+// A fleet of Dense stacks of one shape (dense_serve_fleet.hip): every event names the model that
+// scores it (request word 31), so rows have up to 31 features; one lane, up to DSV_EB events per
+// pass.  The server owns the stacked images, the per-model thresholds and the stats block.
+class DenseFleetServe : public ServeRing {
+ public:
+  // images: n_models images of `stride` floats each, one after the other (ops/serve.py
+  // dense_fleet_serve_images); layers: the one table, offsets relative to a model's image;
+  // thresholds: one per model
+  DenseFleetServe(int device, int nslots, const float* images, int64_t n_models, int64_t stride, int64_t img_floats,
+                  const std::vector<DenseServeLayer>& layers, int D, const std::vector<float>& scale,
+                  const std::vector<float>& shift, const std::vector<float>& thresholds, double idle_seconds);
+  ~DenseFleetServe() override;
+  int64_t n_models() const { return args_.n_models; }
+  int64_t stride() const { return args_.stride; }
+  const char* kernel() const { return "fleet"; }
+  uint64_t passes() const { return stats() >> 32; }
+  uint64_t events() const { return stats() & 0xffffffffull; }
+  // submit + wait + copy for k rows, row i scored by model models[i].  Every index is checked
+  // before anything is published: std::invalid_argument names the first one >= n_models.
+  void infer(const float* rows, const uint32_t* models, int k, float* scores, uint32_t* flags, float* recon,
+             double timeout_s);
+  // the first index >= n_models among models[0 .. k), or -1
+  int64_t first_bad_index(const uint32_t* models, int64_t k) const;
+  // Replace model i's image (stride floats) / the whole stack (n_models * stride floats): stops the
+  // resident kernel and waits until it has left (alive == 0), copies; the next submit relaunches.
+  void set_image(int64_t i, const float* image);
+  void set_images(const float* images);
+
+ protected:
+  hipError_t launch_kernel() override;
+
+ private:
+  static int checked_D(const float* images, int64_t n_models, int64_t stride, int64_t img_floats,
+                       const std::vector<DenseServeLayer>& layers, int D, const std::vector<float>& scale,
+                       const std::vector<float>& shift, const std::vector<float>& thresholds);
+  uint64_t stats() const;
+  void halt();   // stop the resident kernel, wait for alive == 0
+  DenseFleetServeArgs args_{};
+  uint64_t* stats_ = nullptr;   // host-mapped, 128 bytes
+  float* img_d_ = nullptr;
+  float* thr_d_ = nullptr;
+  float* scale_d_ = nullptr;
+  float* shift_d_ = nullptr;
+};
+
 // LSTM forecaster (lstm_serve.hip): per car key, the last T events stay on the device; each
 // event is scored against the key's previous forecast and a new forecast is emitted.
 class LSTMServe : public ServeRing {

@@ -1673,6 +1673,86 @@ struct DenseServePy : ServePy {
   sml::DenseServe& dense() { return *static_cast<sml::DenseServe*>(s.get()); }
 };
 
+// images: [M, stride] stacked weight images; layers: the one table of (in, out, act, w_off, b_off)
+// tuples, offsets relative to a model's image; thresholds: [M].  Keyed by the model index:
+// _io.ScoreLoop drives it through c_api()'s infer_keyed with nkeys = M.
+struct DenseFleetServePy : ServePy {
+  using farray = py::array_t<float, py::array::c_style | py::array::forcecast>;
+  DenseFleetServePy(int device, int nslots, farray images, int64_t img_floats, std::vector<std::vector<int>> layers,
+                    int D, py::object scale, py::object shift, farray thresholds, double idle_seconds) {
+    if (images.ndim() != 2) throw std::invalid_argument("images must be [M, stride]");
+    std::vector<sml::DenseServeLayer> L;
+    for (const auto& t : layers) {
+      if (t.size() != 5) throw std::invalid_argument("layer descriptor: (in, out, act, w_off, b_off)");
+      L.push_back(sml::DenseServeLayer{t[0], t[1], t[2], t[3], t[4]});
+    }
+    std::vector<float> sc, sh;
+    if (!scale.is_none()) {
+      auto a = scale.cast<farray>();
+      auto b = shift.cast<farray>();
+      sc.assign(a.data(), a.data() + a.size());
+      sh.assign(b.data(), b.data() + b.size());
+    }
+    std::vector<float> thr(thresholds.data(), thresholds.data() + thresholds.size());
+    c10::hip::HIPGuard guard(device);
+    s = std::make_unique<sml::DenseFleetServe>(device, nslots, images.data(), (int64_t)images.shape(0),
+                                               (int64_t)images.shape(1), img_floats, L, D, sc, sh, thr,
+                                               idle_seconds);
+  }
+  sml::DenseFleetServe& fleet() { return *static_cast<sml::DenseFleetServe*>(s.get()); }
+  int64_t nkeys() const override { return static_cast<sml::DenseFleetServe*>(s.get())->n_models(); }
+  // [k] integers -> uint32 indices; std::invalid_argument names the first one outside [0, M)
+  std::vector<uint32_t> models_of(const py::object& models, ssize_t n) {
+    auto k = models.cast<py::array_t<int64_t, py::array::c_style | py::array::forcecast>>();
+    if (k.ndim() != 1 || k.shape(0) != n) throw std::invalid_argument("models must be [k] integers, one per row");
+    const int64_t M = nkeys();
+    std::vector<uint32_t> out((size_t)n);
+    for (ssize_t i = 0; i < n; ++i) {
+      const int64_t v = k.data()[i];
+      if (v < 0 || v >= M)
+        throw std::invalid_argument("DenseFleetServe: model index " + std::to_string(v) + " of row " +
+                                    std::to_string(i) + " is outside [0, " + std::to_string(M) + ")");
+      out[(size_t)i] = (uint32_t)v;
+    }
+    return out;
+  }
+  py::tuple infer_models(farray rows, py::object models, bool want_recon, double timeout_s) {
+    if (rows.ndim() != 2 || rows.shape(1) != s->D()) throw std::invalid_argument("rows must be [k, D]");
+    const int k = (int)rows.shape(0);
+    const std::vector<uint32_t> mv = models_of(models, k);
+    py::array_t<float> scores(k);
+    py::array_t<uint32_t> flags(k);
+    py::array_t<float> recon(want_recon ? std::vector<ssize_t>{k, s->D()} : std::vector<ssize_t>{0});
+    const float* src = rows.data();
+    float* ps = scores.mutable_data();
+    uint32_t* pf = flags.mutable_data();
+    float* pr = want_recon ? recon.mutable_data() : nullptr;
+    {
+      py::gil_scoped_release rel;
+      fleet().infer(src, mv.data(), k, ps, pf, pr, timeout_s);
+    }
+    return py::make_tuple(scores, flags, recon);
+  }
+  py::array_t<int64_t> latency_models(farray rows, int64_t gap_ns, py::object models) {
+    if (rows.ndim() != 2 || rows.shape(1) != s->D()) throw std::invalid_argument("rows must be [n, D]");
+    (void)models_of(models, rows.shape(0));   // names the first bad index
+    return latency_run(rows, gap_ns, models);
+  }
+  void set_image(int64_t i, farray image) {
+    if (image.size() != fleet().stride()) throw std::invalid_argument("image must have `stride` floats");
+    const float* p = image.data();
+    py::gil_scoped_release rel;
+    fleet().set_image(i, p);
+  }
+  void set_images(farray images) {
+    if (images.size() != fleet().stride() * fleet().n_models())
+      throw std::invalid_argument("images must be [M, stride]");
+    const float* p = images.data();
+    py::gil_scoped_release rel;
+    fleet().set_images(p);
+  }
+};
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -1923,6 +2003,26 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
                              "passes the kernel ran since construction")
       .def_property_readonly("events", [](DenseServePy& p) { return p.dense().events(); },
                              "events those passes served");
+  py::class_<DenseFleetServePy, ServePy>(
+      m, "DenseFleetServe", "persistent per-event scorer for a fleet of Dense stacks: a model index per event")
+      .def(py::init<int, int, DenseFleetServePy::farray, int64_t, std::vector<std::vector<int>>, int, py::object,
+                    py::object, DenseFleetServePy::farray, double>(),
+           py::arg("device"), py::arg("nslots"), py::arg("images"), py::arg("img_floats"), py::arg("layers"),
+           py::arg("D"), py::arg("scale"), py::arg("shift"), py::arg("thresholds"), py::arg("idle_seconds") = 2.0)
+      .def("infer_models", &DenseFleetServePy::infer_models, py::arg("rows"), py::arg("models"),
+           py::arg("want_recon") = false, py::arg("timeout_s") = 10.0)
+      .def("latency_models", &DenseFleetServePy::latency_models, py::arg("rows"), py::arg("gap_ns"),
+           py::arg("models"))
+      .def("set_image", &DenseFleetServePy::set_image, py::arg("i"), py::arg("image"),
+           "stop the resident kernel, replace model i's image; the next submit relaunches")
+      .def("set_images", &DenseFleetServePy::set_images, py::arg("images"))
+      .def_property_readonly("n_models", [](DenseFleetServePy& p) { return p.fleet().n_models(); })
+      .def_property_readonly("stride", [](DenseFleetServePy& p) { return p.fleet().stride(); })
+      .def_property_readonly("kernel", [](DenseFleetServePy& p) { return std::string(p.fleet().kernel()); })
+      .def_property_readonly("passes", [](DenseFleetServePy& p) { return p.fleet().passes(); })
+      .def_property_readonly("events", [](DenseFleetServePy& p) { return p.fleet().events(); });
+  m.attr("DSV_FLEET_MAXD") = (int)sml::DSV_FLEET_MAXD;
+  m.attr("DSV_FLEET_MAXMODELS") = (int)sml::DSV_FLEET_MAXMODELS;
   m.attr("DSV_MAXW") = (int)sml::DSV_MAXW;
   m.attr("DSV_MAXLAYERS") = (int)sml::DSV_MAXLAYERS;
   m.attr("DSV_EB") = (int)sml::DSV_EB;

@@ -58,10 +58,16 @@ class LowLatencyScorer:
                  config: Optional[Sequence[str]] = None, max_batch: int = 4096, max_bytes: int = 1 << 20,
                  max_wait_ms: int = 100, commit_interval_s: float = 0.0, record_latency: bool = False,
                  framing: bool = True, spin_us: int = 0, source_format: str = "avro", json_stamp: str = "",
-                 hash_ranges: Optional[Sequence] = None):
+                 hash_ranges: Optional[Sequence] = None, key_table: Optional[dict] = None,
+                 unknown_key_id: int = -1):
         """``hash_ranges``: one ``(lo, hi)`` key-hash share per partition (kafka/assign.py
         ``key_shares``); records whose key hashes outside it are another replica's cars
-        (skipped, counted as ``foreign``)."""
+        (skipped, counted as ``foreign``).
+
+        ``key_table`` (keyed scorers): a preset ``{record key (bytes or str) -> id}``, e.g. a fleet
+        scorer's car key -> model index.  With one the loop never assigns ids itself: a key outside
+        the table is scored as ``unknown_key_id``, or -- ``-1`` -- skipped and counted as
+        ``keys_dropped``.  Without one, ids are given first come, first served."""
         client = KafkaClient(servers, config)
         self.partitions = [int(p) for p in partitions]
         if starts is None:   # committed offset of the group, else the log start
@@ -89,7 +95,17 @@ class LowLatencyScorer:
                                          int(max_batch), int(max_bytes), int(max_wait_ms), float(commit_interval_s),
                                          bool(record_latency), int(api), int(spin_us),
                                          json_columns() if source_format == "json" else [], str(json_stamp),
-                                         [(int(lo), int(hi)) for lo, hi in (hash_ranges or [])], reset)
+                                         [(int(lo), int(hi)) for lo, hi in (hash_ranges or [])], reset,
+                                         *self._key_table_args(key_table, unknown_key_id))
+
+    @staticmethod
+    def _key_table_args(key_table, unknown_key_id) -> tuple:
+        if key_table is None:
+            if int(unknown_key_id) != -1:
+                raise ValueError("unknown_key_id goes with a key_table")
+            return ()
+        table = {(k if isinstance(k, bytes) else str(k).encode()): int(v) for k, v in key_table.items()}
+        return table, int(unknown_key_id)
 
     def run(self, max_events: int = 0, idle_timeout_s: Optional[float] = None) -> dict:
         """Blocking (GIL released): until ``stop()``, ``max_events`` or ``idle_timeout_s``

@@ -301,6 +301,11 @@ class DenseFleet:
         buf = np.concatenate([w.ravel() for w in weights])
         self.flat[self._check_index(i), :self.nflat].copy_(torch.from_numpy(buf))
 
+    def server(self, **kw):
+        """A :class:`~streamml.ops.serve.DenseFleetScoringServer` over this fleet's weights as they stand."""
+        from .serve import DenseFleetScoringServer
+        return DenseFleetScoringServer.from_fleet(self, **kw)
+
     def model(self, i: int, device=None):
         """Model ``i`` as a standalone ``nn`` model of the fleet's architecture with its weights, Adam
         moments, iteration and learning rate: it can go on training with ``fit`` (the fleet's

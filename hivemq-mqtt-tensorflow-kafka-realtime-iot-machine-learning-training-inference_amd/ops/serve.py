@@ -1,5 +1,5 @@
 """Persistent per-event scoring on the GPU (``csrc/kernels/ae_serve.hip``, ``dense_serve.hip``,
-``lstm_serve.hip``, ``lstm_serve_wide.hip``).
+``dense_serve_fleet.hip``, ``lstm_serve.hip``, ``lstm_serve_wide.hip``).
 
 ``ScoringServer(model)`` keeps one wave resident on the device that polls a
 host-mapped request ring; ``score(rows)`` publishes rows and spins on the
@@ -11,6 +11,10 @@ without requests and is relaunched transparently on the next request.
 ``DenseScoringServer(model)`` has the same surface for Dense stacks of any depth (1..8 layers
 up to 512 wide: an ``nn.Sequential`` / ``nn.Model`` or an ``Autoencoder``) on a resident
 1024-thread workgroup that serves up to 8 events of a backlog per pass.
+
+``DenseFleetScoringServer(models)`` serves M such stacks of one shape from ONE resident workgroup
+(``dense_serve_fleet.hip``): every row names the member that scores it -- one model per car, as
+``ops.dense_fleet.DenseFleet`` / ``fleet --layers`` train them.
 
 ``LSTMScoringServer(model)`` serves an :class:`~streamml.models.lstm.LSTMPredictor` the
 same way, per car key: the device keeps each key's last ``look_back`` normalised events
@@ -289,6 +293,362 @@ class DenseScoringServer:
             self.close()
         except Exception:
             pass
+
+
+def _dense_flat_offsets(layers) -> list:
+    """(w_off, b_off) of each layer in a flat parameter vector that holds every kernel ``[in, units]``
+    followed by its bias (layers without a bias have none), one layer after the other."""
+    offs, off = [], 0
+    for n_in, n_out, _, use_bias in layers:
+        offs.append((off, off + n_in * n_out))
+        off += n_in * n_out + (n_out if use_bias else 0)
+    return offs
+
+
+def dense_fleet_serve_images(layers, flats_or_weight_lists, offsets=None) -> Tuple[np.ndarray, list]:
+    """Pack the stacked weight images of ``dense_serve_fleet.hip`` for M models of ONE layer table:
+    ``images [M, stride]`` fp32 whose row i equals ``dense_serve_image(layers, weights_i)[0]``,
+    zero-padded to ``stride`` (the image's length rounded up to 4 floats), and the one table of
+    ``(in, units, activation code, w_off, b_off)`` with offsets relative to a model's image.
+
+    ``flats_or_weight_lists``: a ``[M, n]`` array of flat parameters (layer k's kernel at
+    ``offsets[k][0]``, its bias at ``offsets[k][1]``; default: kernels and biases one after the
+    other, as ``FlatParams.flat`` and ``DenseFleet.flat`` hold them), or a sequence of M weight
+    lists as ``dense_layer_table`` returns them.  The packing is numpy over the model axis."""
+    from .dense import ACT
+    layers = list(layers)
+    if isinstance(flats_or_weight_lists, np.ndarray):
+        flats = np.asarray(flats_or_weight_lists, np.float32)
+        if flats.ndim != 2:
+            raise ValueError("flat parameters must be [M, n]")
+    else:
+        if offsets is not None:
+            raise ValueError("offsets go with flat parameters")
+        rows = []
+        for weights in flats_or_weight_lists:   # gathers M separate objects; the packing below has no such loop
+            parts = []
+            for (n_in, n_out, _, use_bias), (W, b) in zip(layers, weights):
+                W = np.asarray(W, np.float32)
+                if W.shape != (n_in, n_out):
+                    raise ValueError(f"kernel of shape {W.shape} for a {n_in} -> {n_out} layer")
+                parts.append(W.ravel())
+                if use_bias:
+                    parts.append(np.asarray(b, np.float32).reshape(n_out))
+            rows.append(np.concatenate(parts))
+        flats = np.stack(rows) if rows else np.zeros((0, 0), np.float32)
+    offsets = _dense_flat_offsets(layers) if offsets is None else list(offsets)
+    M, t = flats.shape[0], DENSE_SERVE_TILE
+    geo = [((i + 3) // 4 * 4, (o + t - 1) // t * t) for i, o, _, _ in layers]
+    img_floats = sum(kp * npad + npad for kp, npad in geo)
+    stride = (img_floats + 3) // 4 * 4
+    images = np.zeros((M, stride), np.float32)
+    table, off = [], 0
+    for (n_in, n_out, act, use_bias), (kp, npad), (w_off, b_off) in zip(layers, geo, offsets):
+        if w_off + n_in * n_out > flats.shape[1] or (use_bias and b_off + n_out > flats.shape[1]):
+            raise ValueError("a layer's parameters lie outside the flat vector")
+        wp = np.zeros((M, kp, npad), np.float32)
+        wp[:, :n_in, :n_out] = flats[:, w_off:w_off + n_in * n_out].reshape(M, n_in, n_out)
+        # [M, Kp, Np] -> [M][Kp / 4][Np][4]: 16 bytes hold rows 4g .. 4g + 3 of one column
+        images[:, off:off + kp * npad] = wp.reshape(M, kp // 4, 4, npad).transpose(0, 1, 3, 2).reshape(M, kp * npad)
+        if use_bias:
+            images[:, off + kp * npad:off + kp * npad + n_out] = flats[:, b_off:b_off + n_out]
+        table.append((n_in, n_out, ACT[act], off, off + kp * npad))
+        off += kp * npad + npad
+    return images, table
+
+
+class DenseFleetScoringServer:
+    """Persistent per-event scorer for a FLEET of Dense stacks of one shape (``dense_serve_fleet.hip``):
+    every row names the member that scores it, ``score(rows, models)``.  One resident workgroup holds
+    the whole fleet: the members' weight images are stacked in device memory and each event reads its
+    own; an event's result bits are those :class:`DenseScoringServer` gives for that member alone.
+
+    ``models``: a sequence of ``nn`` models (or ``Autoencoder``) whose ``dense_layer_table(...)[0]`` are
+    equal.  ``thresholds``: one number or one per member (``flag = score > thresholds[model]``).
+    ``normalizer``: None, ``"cardata"`` or a ``(scale, shift)`` pair, ONE for the whole fleet, the way
+    the fleet trainer normalises.  Limits as :class:`DenseScoringServer`, but rows have at most
+    ``MAX_FEATURES`` = 31 features: request word 31 carries the model index."""
+
+    MAX_WIDTH = DenseScoringServer.MAX_WIDTH
+    MAX_FEATURES = 31    # request word 31 carries the model index
+    MAX_LAYERS = DenseScoringServer.MAX_LAYERS
+    MAX_PASS = DenseScoringServer.MAX_PASS
+    MAX_MODELS = (1 << 24) - 1
+    ACTIVATIONS = DenseScoringServer.ACTIVATIONS
+
+    @staticmethod
+    def supports(model, n_models: int = 1) -> Tuple[bool, str]:
+        """(True, "") if a fleet of ``n_models`` members shaped like ``model`` can be served, else
+        (False, the limit it exceeds).  ``model`` may be a sequence of members: then their layer
+        tables must be equal.  Mirrors ``dense_fleet_serve_check``; needs no device."""
+        S = DenseFleetScoringServer
+        members = list(model) if isinstance(model, (list, tuple)) else [model]
+        if not members:
+            return False, "a fleet must have 1..16777215 models (it has 0)"
+        try:
+            layers, _ = dense_layer_table(members[0])
+        except ValueError as e:
+            return False, str(e)
+        D = layers[0][0] if layers else 0
+        if layers and not 1 <= D <= S.MAX_FEATURES:
+            return False, (f"rows must have 1..{S.MAX_FEATURES} features (request word 31 carries the model index); "
+                           f"it has {D}")
+        ok, why = DenseScoringServer.supports(members[0])
+        if not ok:
+            return False, why
+        why = S.first_difference(members)
+        if why:
+            return False, why
+        if not 1 <= int(n_models) <= S.MAX_MODELS:
+            return False, f"a fleet must have 1..{S.MAX_MODELS} models (it has {int(n_models)})"
+        return True, ""
+
+    @staticmethod
+    def first_difference(models) -> str:
+        """Empty if the members share one layer table, else the first model and layer that differ."""
+        ref, _ = dense_layer_table(models[0])
+        for i, mdl in enumerate(models[1:], start=1):
+            try:
+                layers, _ = dense_layer_table(mdl)
+            except ValueError as e:
+                return f"model {i}: {e}"
+            if len(layers) != len(ref):
+                return f"model {i} has {len(layers)} Dense layers, model 0 has {len(ref)}"
+            for l, (a, b) in enumerate(zip(ref, layers)):
+                if a != b:
+                    return (f"model {i} differs from model 0 in layer {l}: (in, units, activation, use_bias) = "
+                            f"{b} != {a}")
+        return ""
+
+    def __init__(self, models, thresholds=5.0, slots: int = 4096, idle_seconds: float = 2.0, normalizer=None,
+                 device: Optional[torch.device] = None):
+        models = list(models)
+        if not models:
+            raise ValueError("a fleet needs at least one model")
+        ok, why = self.supports(models, len(models))
+        if not ok:
+            raise ValueError(f"DenseFleetScoringServer cannot serve this fleet: {why}")
+        layers, _ = dense_layer_table(models[0])
+        images, table = dense_fleet_serve_images(layers, [dense_layer_table(m)[1] for m in models])
+        dev = device if device is not None else models[0].device
+        self._open(layers, images, table, thresholds, slots, idle_seconds, normalizer, dev)
+
+    def _open(self, layers, images, table, thresholds, slots, idle_seconds, normalizer, device) -> None:
+        dev = torch.device(device)
+        if dev.type != "cuda":
+            raise RuntimeError("DenseFleetScoringServer needs a ROCm device (use model.predict on CPU)")
+        self.layers = list(layers)
+        self.D = int(layers[0][0])
+        M = int(images.shape[0])
+        thr = np.asarray(thresholds, np.float32)
+        thr = np.full(M, float(thr), np.float32) if thr.ndim == 0 else np.ascontiguousarray(thr.reshape(-1))
+        if thr.shape != (M,):
+            raise ValueError(f"thresholds must be one number or [{M}], one per model")
+        self.thresholds = thr
+        sc = sh = None
+        if isinstance(normalizer, str) and normalizer == "cardata":
+            from ..data.cardata import normalize_affine
+            if self.D != 18:
+                raise ValueError(f"the cardata normaliser needs 18 features (the models have {self.D})")
+            sc, sh = normalize_affine()
+        elif normalizer is not None and not (isinstance(normalizer, str) and normalizer == "none"):
+            if isinstance(normalizer, str) or len(normalizer) != 2:
+                raise ValueError(f"unknown normalizer {normalizer!r}")
+            sc, sh = normalizer
+        if sc is not None:
+            sc, sh = np.asarray(sc, np.float32).reshape(-1), np.asarray(sh, np.float32).reshape(-1)
+            if sc.size != self.D or sh.size != self.D:
+                raise ValueError(f"normalizer scale / shift must have {self.D} entries")
+        C = load_c()
+        assert (C.DSV_FLEET_MAXD, C.DSV_FLEET_MAXMODELS - 1) == (self.MAX_FEATURES, self.MAX_MODELS)
+        t = DENSE_SERVE_TILE
+        img_floats = sum(((i + 3) // 4 * 4 + 1) * ((o + t - 1) // t * t) for i, o, _, _ in layers)
+        self._s = C.DenseFleetServe(dev.index if dev.index is not None else torch.cuda.current_device(), int(slots),
+                                    np.ascontiguousarray(images, np.float32), int(img_floats),
+                                    [list(r) for r in table], self.D, sc, sh, thr, float(idle_seconds))
+
+    @classmethod
+    def from_fleet(cls, fleet, **kw) -> "DenseFleetScoringServer":
+        """Serve a :class:`~streamml.ops.dense_fleet.DenseFleet` as it stands: ``fleet.flat`` is read once."""
+        self = cls.__new__(cls)
+        layers, images, table = cls._fleet_images(fleet)
+        ok, why = cls.supports(fleet._template, fleet.n_models)
+        if not ok:
+            raise ValueError(f"DenseFleetScoringServer cannot serve this fleet: {why}")
+        self._open(layers, images, table, kw.pop("thresholds", 5.0), kw.pop("slots", 4096),
+                   kw.pop("idle_seconds", 2.0), kw.pop("normalizer", None), kw.pop("device", fleet.device))
+        if kw:
+            raise TypeError(f"unexpected arguments {sorted(kw)}")
+        return self
+
+    @classmethod
+    def from_flats(cls, layers, flats, offsets=None, thresholds=5.0, slots: int = 4096, idle_seconds: float = 2.0,
+                   normalizer=None, device=None) -> "DenseFleetScoringServer":
+        """Serve M members given as flat parameter vectors ``flats [M, n]`` of the layer table ``layers``
+        (``dense_layer_table(model)[0]``), without building M model objects; ``offsets`` as in
+        :func:`dense_fleet_serve_images`."""
+        self = cls.__new__(cls)
+        images, table = dense_fleet_serve_images(layers, np.asarray(flats, np.float32), offsets=offsets)
+        if device is None:
+            device = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else "cpu"
+        self._open(list(layers), images, table, thresholds, slots, idle_seconds, normalizer, device)
+        return self
+
+    @staticmethod
+    def _fleet_images(fleet):
+        layers, _ = dense_layer_table(fleet._template)
+        offsets = [(int(r[6]), int(r[7])) for r in fleet.table]   # (w_off, b_off) in a member's flat
+        flats = fleet.flat.detach().cpu().numpy()                  # one device -> host copy
+        images, table = dense_fleet_serve_images(layers, flats, offsets=offsets)
+        return layers, images, table
+
+    @classmethod
+    def from_dir(cls, path, **kw) -> "DenseFleetScoringServer":
+        """Serve the directory ``fleet --layers`` wrote: ``index.json`` names the members' files and
+        the car keys each one owns.  ``names[i]`` is member i's name and ``key_to_model`` maps a car
+        key to its member's index."""
+        models, names, key_to_model = cls.load_dir(path)
+        if kw.get("device", None) is None:
+            kw["device"] = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else "cpu"
+        self = cls(models, **kw)
+        self.names, self.key_to_model = names, key_to_model
+        return self
+
+    @classmethod
+    def load_dir(cls, path) -> Tuple[list, list, dict]:
+        """What ``from_dir`` reads before it opens a device: (members as CPU models, names,
+        key_to_model).  Raises ``ValueError`` for a directory without ``layers`` in its index or
+        with members ``supports`` rejects."""
+        names, files, key_to_model = read_fleet_index(path)
+        from ..nn.model import load_model
+        models = [load_model(f, device="cpu", compile=False) for f in files]
+        ok, why = cls.supports(models, len(models))
+        if not ok:
+            raise ValueError(f"{path}: the persistent fleet scorer cannot serve these models: {why}")
+        return models, names, key_to_model
+
+    def _rows_models(self, rows, models):
+        rows = np.ascontiguousarray(np.asarray(rows, np.float32).reshape(-1, self.D))
+        idx = np.ascontiguousarray(np.asarray(models, np.int64).reshape(-1))
+        if idx.size != rows.shape[0]:
+            raise ValueError(f"{idx.size} model indices for {rows.shape[0]} rows")
+        return rows, idx
+
+    def score(self, rows, models) -> Tuple[np.ndarray, np.ndarray]:
+        """(scores [k], anomaly flags [k]) for raw rows [k, D], row i scored by member ``models[i]``.
+        An index outside ``[0, n_models)`` raises ``ValueError`` before anything is published."""
+        rows, idx = self._rows_models(rows, models)
+        s, f, _ = self._s.infer_models(rows, idx, False, 10.0)
+        return s, f.astype(bool)
+
+    def infer(self, rows, models) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """(scores, flags, reconstructions [k, D])."""
+        rows, idx = self._rows_models(rows, models)
+        s, f, r = self._s.infer_models(rows, idx, True, 10.0)
+        return s, f.astype(bool), r
+
+    def latency_us(self, rows, models, qps: float = 10000.0, device_breakdown: bool = False):
+        """Per-event latency (us) of rows submitted one at a time at ``qps`` (C++ timing loop);
+        with ``device_breakdown`` also the on-device processing time of each event (us)."""
+        rows, idx = self._rows_models(rows, models)
+        gap = int(1e9 / qps) if qps > 0 else 0
+        out = self._s.latency_models(rows, gap, idx) / 1e3
+        if device_breakdown:   # (host round trip, device total, device row-load, device compute)
+            return out[:, 0], out[:, 1], out[:, 2], out[:, 3]
+        return out[:, 0]
+
+    def set_weights(self, i: int, weights) -> None:
+        """Replace member i's weights (a Keras-order list as ``model.get_weights()`` gives, or the
+        ``(W, b)`` pairs of ``dense_layer_table``): the resident kernel is stopped, the image copied,
+        and the next call relaunches it."""
+        weights = list(weights)
+        if weights and not isinstance(weights[0], (tuple, list)):
+            it, pairs = iter(weights), []
+            for _, _, _, use_bias in self.layers:
+                W = next(it)
+                pairs.append((W, next(it) if use_bias else None))
+            weights = pairs
+        images, _ = dense_fleet_serve_images(self.layers, [weights])
+        if not 0 <= int(i) < self.n_models:
+            raise ValueError(f"model index {int(i)} is outside [0, {self.n_models})")
+        self._s.set_image(int(i), images[0])
+
+    def refresh(self, fleet) -> None:
+        """Take every member's weights from ``fleet`` again (after further training)."""
+        layers, images, _ = self._fleet_images(fleet)
+        if list(layers) != self.layers or images.shape[0] != self.n_models:
+            raise ValueError("the fleet's shape differs from the one being served")
+        self._s.set_images(images)
+
+    @property
+    def n_models(self) -> int:
+        return int(self._s.n_models)
+
+    @property
+    def stride(self) -> int:
+        """Floats between two members' weight images in device memory."""
+        return int(self._s.stride)
+
+    @property
+    def kernel(self) -> str:
+        """Always "fleet": the images stay in device memory."""
+        return str(self._s.kernel)
+
+    @property
+    def passes(self) -> int:
+        """Passes the kernel ran since construction (one pass serves 1 .. ``MAX_PASS`` events)."""
+        return int(self._s.passes)
+
+    @property
+    def events(self) -> int:
+        """Events those passes served."""
+        return int(self._s.events)
+
+    @property
+    def launches(self) -> int:
+        return int(self._s.launches)
+
+    def close(self) -> None:
+        if getattr(self, "_s", None) is not None:
+            self._s.stop()
+            self._s = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def read_fleet_index(path) -> Tuple[list, list, dict]:
+    """(names, files, key_to_model) of a ``fleet --layers`` directory: the members in ``index.json``'s
+    order (its ``INDEX_META`` keys skipped), their ``.h5`` paths and car key -> member index.
+    Raises ``ValueError`` for a directory the Dense fleet trainer did not write."""
+    import json
+    import os
+    from ..cli.fleet import INDEX_META
+    idx_path = os.path.join(str(path), "index.json")
+    if not os.path.isfile(idx_path):
+        raise ValueError(f"{path}: no index.json (expected the output directory of fleet --layers)")
+    with open(idx_path) as f:
+        index = json.load(f)
+    if "layers" not in index:
+        raise ValueError(f"{path}: index.json has no 'layers' (the directory was not written by fleet --layers)")
+    names = [n for n in index if n not in INDEX_META]
+    if not names:
+        raise ValueError(f"{path}: index.json names no model")
+    files = [os.path.join(str(path), index[n]["file"]) for n in names]
+    key_to_model = {}
+    for i, n in enumerate(names):
+        for k in index[n].get("keys", []):
+            key_to_model[str(k)] = i
+    return names, files, key_to_model
 
 
 def lstm_layer_table(model) -> Tuple[np.ndarray, list]:
