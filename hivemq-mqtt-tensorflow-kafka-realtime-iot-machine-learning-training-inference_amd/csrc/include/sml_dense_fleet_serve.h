@@ -1,10 +1,10 @@
 // The per-event Dense scorers' limits and layer table (kernels/dense_serve.hip: one model;
 // kernels/dense_serve_fleet.hip: a fleet of models of one shape, a model index per event), the fleet
-// kernel's arguments and the check that says which fleets it takes.  Plain C++17 with no HIP header,
-// so a host program can include it and ask the check without a GPU
-// (csrc/tests/dense_fleet_serve_check.cpp).  ops/serve.py mirrors the check in Python, because
-// supports() must answer without a built extension; tests/test_dense_fleet_serve.py holds the two
-// together on the CPU.  sml_ops.h includes this header: the single-model scorer reads the same limits.
+// kernel's arguments and the checks that say which stacks and fleets they take.  Plain C++17 with no
+// HIP header, so a host program can include it and ask the checks without a GPU
+// (csrc/tests/dense_fleet_serve_check.cpp).  ops/serve.py mirrors the checks in Python, because
+// supports() must answer without a built extension; tests/test_dense_serve_limits.py and
+// tests/test_dense_fleet_serve.py hold the two together on the CPU.  sml_ops.h includes this header.
 #pragma once
 
 #include <cstdint>
@@ -80,13 +80,12 @@ struct DenseFleetServeArgs {
 // floats between two images of a fleet whose single image has img_floats floats
 constexpr int64_t dense_fleet_serve_stride(int64_t img_floats) { return (img_floats + 3) / 4 * 4; }
 
-// empty if the fleet kernel can serve n_models stacks of this table (D features, nl layers, offsets
-// inside an image of img_floats floats, images stride floats apart), else the limit it exceeds:
-// the single-model scorer's rules (dense_serve_check) with rows of at most 31 features, plus the
-// stride's and the fleet size's
-inline const char* dense_fleet_serve_check(const DenseServeLayer* L, int nl, int D, int64_t img_floats, int64_t stride,
-                                           int64_t n_models) {
-  if (D < 1 || D > DSV_FLEET_MAXD) return "rows must have 1..31 features (request word 31 carries the model index)";
+// The layer-table rules of both scorers: empty if a stack of this table (D features in rows of at
+// most max_D, nl layers, offsets inside an image of img_floats floats) can be served, else the limit
+// it exceeds (rows_why: the message of the row limit)
+inline const char* dense_serve_check_rows(const DenseServeLayer* L, int nl, int D, int64_t img_floats, int max_D,
+                                          const char* rows_why) {
+  if (D < 1 || D > max_D) return rows_why;
   if (nl < 1 || nl > DSV_MAXLAYERS) return "the stack must have 1..8 Dense layers";
   int dim = D;
   int64_t total = 0;
@@ -103,6 +102,30 @@ inline const char* dense_fleet_serve_check(const DenseServeLayer* L, int nl, int
   }
   if (dim != D) return "the last layer must have one unit per feature";
   if (img_floats != total) return "the weight image has the wrong length";
+  return "";
+}
+
+// empty if the single-model kernel can serve the stack, else the limit it exceeds
+inline const char* dense_serve_check(const DenseServeLayer* L, int nl, int D, int64_t img_floats) {
+  return dense_serve_check_rows(L, nl, D, img_floats, 32, "rows must have 1..32 features (a request slot holds 32 words)");
+}
+
+// the single-model kernel copies the whole image to LDS: a pure function of the layer table and
+// DSV_LDS_IMAGE_BYTES
+inline bool dense_serve_in_lds(const DenseServeLayer* L, int nl) {
+  int64_t bytes = 0;
+  for (int l = 0; l < nl && l < DSV_MAXLAYERS; ++l) bytes += 4 * (int64_t)dense_serve_layer_floats(L[l].in, L[l].out);
+  return bytes <= DSV_LDS_IMAGE_BYTES;
+}
+
+// empty if the fleet kernel can serve n_models stacks of this table (images stride floats apart),
+// else the limit it exceeds: the single-model rules with rows of at most 31 features, then the
+// stride's and the fleet size's
+inline const char* dense_fleet_serve_check(const DenseServeLayer* L, int nl, int D, int64_t img_floats, int64_t stride,
+                                           int64_t n_models) {
+  const char* why = dense_serve_check_rows(L, nl, D, img_floats, DSV_FLEET_MAXD,
+                                           "rows must have 1..31 features (request word 31 carries the model index)");
+  if (why[0]) return why;
   if (stride % 4 != 0 || stride < img_floats)
     return "the image stride must be a multiple of 4 floats and at least one image long";
   if (n_models < 1 || n_models >= DSV_FLEET_MAXMODELS) return "a fleet must have 1..16777215 models";

@@ -353,11 +353,10 @@ struct DenseServeArgs {
   uint64_t idle_ticks;
   uint64_t* stats;     // host-mapped: {passes << 32 | events}, cumulative, stored after each pass
 };
-// empty if the kernel can serve the stack (D features, nl layers, offsets inside an image of
-// img_floats floats), else the limit it exceeds
-const char* dense_serve_check(const DenseServeLayer* L, int nl, int D, int64_t img_floats);
-// the whole image goes to LDS: a pure function of the layer table and DSV_LDS_IMAGE_BYTES
-bool dense_serve_in_lds(const DenseServeLayer* L, int nl);
+// dense_serve_check (inline, sml_dense_fleet_serve.h): empty if the kernel can serve the stack (D
+// features, nl layers, offsets inside an image of img_floats floats), else the limit it exceeds
+// dense_serve_in_lds (inline, there): the whole image goes to LDS: a pure function of the layer
+// table and DSV_LDS_IMAGE_BYTES
 hipError_t dense_serve_launch(const DenseServeArgs& args, hipStream_t stream);
 
 // ---- persistent per-event scorer for a fleet of Dense stacks (dense_serve_fleet.hip) ----

@@ -2,68 +2,31 @@
 // up to 512, rows of up to 32 features, the last layer one unit per feature (an autoencoder
 // wider or deeper than the reference's 18-14-7-7-18, which ae_serve.hip is built around).
 //
-// Same protocol and semantics as ae_serve.hip: LL-framed request / result slots (sml_ops.h),
-// xn = x * scale + shift, y = stack(xn), score = mean((y - xn)^2) over the D features,
-// flag = score > threshold, the three timing words, `done`, `alive`, `stop` and the idle
-// timeout.  fp32 throughout (the score is compared against a threshold).
+// The ring protocol, the pass, a layer's reduction, the exit conditions and the BIT-IDENTITY
+// argument are described in sml_dense_serve_dev.h, shared with dense_serve_fleet.hip.  Here:
 //
-// One workgroup of 1024 threads.  The weights are an IMAGE built once per server
-// (ops/serve.py: dense_serve_image): per layer float4 img[Kp / 4][Np] with img[g][o] =
-// W[4g .. 4g + 3][o] (Kp = in rounded up to 4, Np = out rounded up to 32, zero-padded),
-// followed by the padded bias [Np]; threads of consecutive o load consecutive 16 bytes.  The
-// kernel body is a template on where that image lives:
+// The weights are an IMAGE built once per server (ops/serve.py: dense_serve_image): per layer
+// float4 img[Kp / 4][Np] with img[g][o] = W[4g .. 4g + 3][o] (Kp = in rounded up to 4, Np = out
+// rounded up to 32, zero-padded), followed by the padded bias [Np]; threads of consecutive o load
+// consecutive 16 bytes.  The kernel body is a template on where that image lives:
 //   "lds"     the whole image is copied to LDS at launch (it fits beside the activation and
 //             partial-sum buffers: DSV_LDS_IMAGE_BYTES);
 //   "stream"  every pass streams the image from L2.
 //
-// A PASS serves E events at once, 1 <= E <= EB = 8.  Waves 0..3 poll the next request slot
-// together with the host's head counter.  With one event outstanding E = 1 and the row has
-// arrived with the poll; with a backlog E = min(head - tail, EB) and wave e fetches row e
-// (rows below head were published before it; tag check, bounded spin).  Per layer the Np
-// output columns times KS slices of the reduction are spread over the threads (KS: a power
-// of two fixed by the layer's shape, dense_serve_k_slices); a thread loads each weight group
-// once and uses it for every event of the pass, reading the events' activations as broadcast
-// float4 from LDS into per-event accumulators (registers: the loops over events are fully
-// unrolled).  The partial sums meet in LDS, are added to the bias in slice order 0 .. KS - 1,
-// and the activation is applied.  Two workgroup barriers per layer.
-//
-// BIT-IDENTITY.  The sum of one output of one event is bias + p_0 + .. + p_{KS-1}, each p_s
-// one fmaf chain over the slice's rows in order from 0.0f: it depends on the layer's shape
-// only, never on E or on the event's position in the pass.  The pass is instantiated for 1,
-// 2, 4 and 8 accumulators (E is rounded up; the surplus accumulators read stale activations
-// and their results are dropped), every instantiation with the same chains, and the score is
-// computed by one wave per event with the same lane-butterfly.  So an event's result bits do
-// not depend on how the ring happened to batch it.
-//
-// After each pass thread 0 stores `done` and ONE 8-byte word {passes << 32 | events}
-// (cumulative over launches) into the server's host-mapped stats block, after the pass's
-// result words were issued: tests read it to prove which path ran.
-//
-// Exit conditions every wave reaches: the host's stop flag or `idle` without a request, decided
-// by wave 0 every 64 polls and broadcast through LDS at the next barrier.  Every branch around
-// a barrier is block-uniform: it depends only on kernel arguments and on values broadcast
-// through LDS (quit, E).  Every spin on host memory is bounded.
-#include "sml_common.h"
-#include "sml_ops.h"
-#include "sml_serve_dev.h"
+// A thread loads each weight group of its slice once and uses it for every event of the pass,
+// reading the events' activations as broadcast float4 from LDS into per-event accumulators
+// (registers: the loops over events are fully unrolled).  The pass is instantiated for 1, 2, 4 and
+// 8 accumulators (E is rounded up; the surplus accumulators read stale activations and their
+// results are dropped), every instantiation with the same chains.
+#include "sml_dense_serve_dev.h"
 
 namespace sml {
 namespace {
 
-using namespace serve_dev;
+using namespace dense_serve_dev;
 
-constexpr int NT = DSV_NT, EB = DSV_EB;
-constexpr int AS = DSV_MAXW;             // stride of an event's activations in LDS (floats)
-constexpr int ACT_FLOATS = EB * AS;      // one activation buffer
-constexpr int PART_FLOATS = EB * NT;     // partial sums [KS][EB][Np], Np * KS <= NT
-constexpr int FIXED_FLOATS = 2 * ACT_FLOATS + PART_FLOATS;   // dynamic LDS before the image
-
-static_assert(DSV_MAXW % 4 == 0 && DSV_MAXW % DSV_TILE == 0, "padded widths stay within DSV_MAXW");
 static_assert(FIXED_FLOATS * 4 + DSV_LDS_IMAGE_BYTES + 2048 <= 160 * 1024, "LDS budget");
-
-__device__ __forceinline__ float fma4(const float4 x, const float4 w, float a) {
-  return fmaf(x.w, w.w, fmaf(x.z, w.z, fmaf(x.y, w.y, fmaf(x.x, w.x, a))));
-}
+static_assert(ACT_LINEAR == 0 && DSV_ACT_LAST == ACT_SIGMOID, "the check's activation range is Act's");
 
 // One layer for EC accumulators (events 0 .. EC - 1 of the pass): in -> out, both in LDS with
 // strides in_s / AS.  W: the layer's image, bias: its padded bias (LDS or global).
@@ -103,14 +66,7 @@ __device__ __forceinline__ void layer_pass(const float4* __restrict__ W, const f
 #pragma unroll
     for (int e = 0; e < EC; ++e) part[(ks * EB + e) * Np + o] = acc[e];
   }
-  __syncthreads();
-  for (int it = tid; it < EC * Np; it += NT) {
-    const int e = it / Np, o = it - e * Np;
-    float s = bias[o];
-    for (int ks = 0; ks < KS; ++ks) s += part[(ks * EB + e) * Np + o];
-    out[e * AS + o] = o < out_n ? act_fwd(act, s) : 0.f;   // padded columns feed zero rows
-  }
-  __syncthreads();
+  layer_finish([bias](int) { return bias; }, EC, Np, KS, DenseLayerOut{out_n, act}, out, part, tid);
 }
 
 template <bool LDSW>
@@ -145,11 +101,7 @@ __global__ __launch_bounds__(DSV_NT) void dense_serve_kernel(DenseServeArgs a) {
   uint64_t last = __builtin_amdgcn_s_memrealtime();
   if (tid == 0) st_sys32(&ctl->alive, 1u);
   for (;;) {
-    // ---------------- waves 0..3 poll the next request slot as in lstm_serve_wide.hip (staggered,
-    // one synchronous cache-bypassing load per poll: lanes 0..31 the slot's words, lanes
-    // 32..63 the host's head counter); the other waves wait at the barrier.  Two polling waves
-    // may find the row at once and publish the same row and (possibly) different E: the barrier
-    // below orders both before any reader, so every thread sees ONE value of E.
+    // ---------------- waves 0..3 poll the next request slot
     const int slot = (int)(tail % (uint64_t)a.nslots);
     const uint32_t want = (uint32_t)(tail + 1);
     if (wid < 4) {
@@ -241,58 +193,20 @@ __global__ __launch_bounds__(DSV_NT) void dense_serve_kernel(DenseServeArgs a) {
       const float se = wave_sum(__fmul_rn(d, d));
       if (lane < D) st_sys(&r->w[lane], tagged(tag, yv));
       if (lane == 0) {
-        const float score = se / (float)D;
-        st_sys(&r->w[kServeScore], tagged(tag, score));
-        st_sys(&r->w[kServeFlag], tagged_u(tag, score > a.threshold ? 1u : 0u));
-        st_sys(&r->w[kServeTLoad], tagged_u(tag, (uint32_t)(t_load - t_seen)));
-        st_sys(&r->w[kServeTComp], tagged_u(tag, (uint32_t)(t_comp - t_seen)));
-        st_sys(&r->w[kServeTDone], tagged_u(tag, (uint32_t)(__builtin_amdgcn_s_memrealtime() - t_seen)));
+        const float score = pass_score_word(r, tag, D, se);
+        pass_flag_words(r, tag, score > a.threshold, t_seen, t_load, t_comp);
       }
     }
     tail += (uint64_t)E;
     passes += 1u;
     events += (uint32_t)E;
     last = __builtin_amdgcn_s_memrealtime();
-    // every wave has issued its result stores and is done with s_xn / s_ctl before the next poll
-    __syncthreads();
-    if (tid == 0) {
-      st_sys(&ctl->done, tail);   // back-pressure hint only: results carry their own tags
-      st_sys(a.stats, ((uint64_t)passes << 32) | (uint64_t)events);
-    }
+    pass_done(ctl, a.stats, tail, passes, events, tid);
   }
-  __syncthreads();
-  wait_stores();
-  if (tid == 0) st_sys32(&ctl->alive, 0u);
+  pass_exit(ctl, tid);
 }
 
 }  // namespace
-
-const char* dense_serve_check(const DenseServeLayer* L, int nl, int D, int64_t img_floats) {
-  if (D < 1 || D > 32) return "rows must have 1..32 features (a request slot holds 32 words)";
-  if (nl < 1 || nl > DSV_MAXLAYERS) return "the stack must have 1..8 Dense layers";
-  int dim = D;
-  int64_t total = 0;
-  for (int l = 0; l < nl; ++l) {
-    if (L[l].out < 1 || L[l].out > DSV_MAXW) return "Dense layers must have 1..512 units";
-    if (L[l].in != dim) return "a layer's input width must match the layer below";
-    if (L[l].act < ACT_LINEAR || L[l].act > ACT_SIGMOID) return "activations must be linear, relu, tanh or sigmoid";
-    const int64_t wn = (int64_t)dense_serve_kp(L[l].in) * dense_serve_np(L[l].out);
-    if (L[l].w_off < 0 || (L[l].w_off & 3) || (int64_t)L[l].w_off + wn > img_floats || L[l].b_off < 0 ||
-        (L[l].b_off & 3) || (int64_t)L[l].b_off + dense_serve_np(L[l].out) > img_floats)
-      return "a layer's weights lie outside the weight image";
-    total += dense_serve_layer_floats(L[l].in, L[l].out);
-    dim = L[l].out;
-  }
-  if (dim != D) return "the last layer must have one unit per feature";
-  if (img_floats != total) return "the weight image has the wrong length";
-  return "";
-}
-
-bool dense_serve_in_lds(const DenseServeLayer* L, int nl) {
-  int64_t bytes = 0;
-  for (int l = 0; l < nl && l < DSV_MAXLAYERS; ++l) bytes += 4 * (int64_t)dense_serve_layer_floats(L[l].in, L[l].out);
-  return bytes <= DSV_LDS_IMAGE_BYTES;
-}
 
 hipError_t dense_serve_launch(const DenseServeArgs& args, hipStream_t stream) {
   if (dense_serve_check(args.L, args.nl, args.D, args.img_floats)[0] || args.nslots < 64 || !args.img || !args.stats)

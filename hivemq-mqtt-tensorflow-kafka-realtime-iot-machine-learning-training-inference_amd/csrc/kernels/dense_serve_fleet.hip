@@ -1,22 +1,19 @@
 // Persistent per-event scorer for a FLEET of Dense stacks of one shape: every event names the
 // model that scores it (one autoencoder per car, ops/dense_fleet.py trains them).
 //
-// Protocol, result words, timing words, `done` / `alive` / `stop`, the idle timeout and the stats
-// word are those of dense_serve.hip, and so is the arithmetic: xn = x * scale + shift (one pair
-// for the whole fleet), y = stack_m(xn), score = mean((y - xn)^2), flag = score > thr[m].  What
-// differs:
+// The ring protocol, the pass, a layer's reduction, the exit conditions and the BIT-IDENTITY
+// argument are described in sml_dense_serve_dev.h (KEYED), shared with dense_serve.hip.  What
+// differs here:
 //   * request word 31 carries the event's model index m as a tagged uint32, so rows have 1..31
 //     features.  The host is the only writer of the ring and refuses m >= n_models before it
 //     publishes (runtime/serve.cpp: DenseFleetServe::infer); the kernel trusts the word.
 //   * the weights are n_models images stacked in device memory, img[n_models][stride], each laid
 //     out as dense_serve.hip's single image; ONE layer table holds offsets relative to a model's
 //     image.  They are always read from memory (L2 / HBM): a fleet does not fit the LDS.
-//   * thr is a device array [n_models].
+//   * thr is a device array [n_models]: flag = score > thr[m].  One scale / shift pair for the fleet.
 //
-// One workgroup of 1024 threads.  A PASS serves E events, 1 <= E <= EB = 8, picked up as in
-// dense_serve.hip; the wave that fetches a row also fetches its model index into LDS.  Events
-// cannot share a weight load, so per layer a thread (slice ks, column o) walks the pass's events
-// in chunks of up to four: each event of a chunk has its own weight pointer and its own
+// Events cannot share a weight load, so per layer a thread (slice ks, column o) walks the pass's
+// events in chunks of up to four: each event of a chunk has its own weight pointer and its own
 // accumulator, and the chunk keeps 2 (four events) or 4 (one or two events) 16-byte weight loads
 // per event in flight -- at most eight float4 of weights, which leaves launch_bounds(1024)'s 128
 // VGPRs without a private segment.  A chunk of three runs the four-event body with the third
@@ -25,39 +22,14 @@
 // There is no separate path for a pass whose events all name one model: sharing its weight loads
 // through dense_serve.hip's layer_pass beside this code needed a private segment in every unroll
 // tried, and a pass of one event is already that kernel's loop (slice_chunk<1, 4>).
-//
-// BIT-IDENTITY.  The sum of one output of one event is bias_m[o] + p_0 + .. + p_{KS-1}, each p_s
-// one fma4 chain over the slice's groups g0 .. g1 in order from 0.0f, with KS, g0 and g1 as in
-// dense_serve.hip's layer_pass: the result bits are those of the single-model server holding
-// model m, whatever E, the chunking or the event's position in the pass.
-//
-// Exit conditions every wave reaches: the host's stop flag or `idle` without a request, decided
-// by wave 0 every 64 polls and broadcast through LDS at the next barrier.  Every branch around a
-// barrier is block-uniform (kernel arguments, quit, E).  Every spin on host memory is bounded.
-#include "sml_common.h"
-#include "sml_ops.h"
-#include "sml_serve_dev.h"
+#include "sml_dense_serve_dev.h"
 
 namespace sml {
 namespace {
 
-using namespace serve_dev;
+using namespace dense_serve_dev;
 
-// the LDS geometry of a pass, as in dense_serve.hip
-constexpr int NT = DSV_NT, EB = DSV_EB;
-constexpr int AS = DSV_MAXW;             // stride of an event's activations in LDS (floats)
-constexpr int ACT_FLOATS = EB * AS;      // one activation buffer
-constexpr int PART_FLOATS = EB * NT;     // partial sums [KS][EB][Np], Np * KS <= NT
-constexpr int LDS_FLOATS = 2 * ACT_FLOATS + PART_FLOATS;   // no image in LDS
-constexpr int KEYW = 31;                 // request word of the model index
-
-static_assert(DSV_MAXW % 4 == 0 && DSV_MAXW % DSV_TILE == 0, "padded widths stay within DSV_MAXW");
-static_assert(LDS_FLOATS * 4 + 2048 <= 160 * 1024, "LDS budget");
 static_assert(DSV_FLEET_MAXD == KEYW, "the model index follows the widest row");
-
-__device__ __forceinline__ float fma4(const float4 x, const float4 w, float a) {
-  return fmaf(x.w, w.w, fmaf(x.z, w.z, fmaf(x.y, w.y, fmaf(x.x, w.x, a))));
-}
 
 // Partial sums of slice [g0, g1) of column o for EC events starting at e0, GU weight groups per
 // event in flight.  Events e0 .. e0 + n - 1 exist (1 <= n <= EC); the surplus accumulators repeat
@@ -125,14 +97,7 @@ __device__ __forceinline__ void fleet_layer(const float* __restrict__ img, size_
       else slice_chunk<4, 2>(img, stride, L.w_off, model, e0, n, g0, g1, Np, o, in, in_s, part_ko);
     }
   }
-  __syncthreads();
-  for (int it = tid; it < E * Np; it += NT) {
-    const int e = it / Np, o = it - e * Np;
-    float s = (img + (size_t)model[e] * stride + L.b_off)[o];
-    for (int ks = 0; ks < KS; ++ks) s += part[(ks * EB + e) * Np + o];
-    out[e * AS + o] = o < L.out ? act_fwd(L.act, s) : 0.f;   // padded columns feed zero rows
-  }
-  __syncthreads();
+  layer_finish([img, stride, model, &L](int e) { return img + (size_t)model[e] * stride + L.b_off; }, E, Np, KS, L, out, part, tid);
 }
 
 __global__ __launch_bounds__(DSV_NT) void dense_serve_fleet_kernel(DenseFleetServeArgs a) {
@@ -162,8 +127,7 @@ __global__ __launch_bounds__(DSV_NT) void dense_serve_fleet_kernel(DenseFleetSer
   uint64_t last = __builtin_amdgcn_s_memrealtime();
   if (tid == 0) st_sys32(&ctl->alive, 1u);
   for (;;) {
-    // ---------------- waves 0..3 poll the next request slot as in dense_serve.hip: lanes 0..31 the
-    // slot's words (word 31: the model index), lanes 32..63 the host's head counter
+    // ---------------- waves 0..3 poll the next request slot (word 31: the model index)
     const int slot = (int)(tail % (uint64_t)a.nslots);
     const uint32_t want = (uint32_t)(tail + 1);
     if (wid < 4) {
@@ -257,28 +221,17 @@ __global__ __launch_bounds__(DSV_NT) void dense_serve_fleet_kernel(DenseFleetSer
       const float se = wave_sum(__fmul_rn(d, d));
       if (lane < D) st_sys(&r->w[lane], tagged(tag, yv));
       if (lane == 0) {
-        const float score = se / (float)D;
-        st_sys(&r->w[kServeScore], tagged(tag, score));
-        st_sys(&r->w[kServeFlag], tagged_u(tag, score > a.thr[s_model[wid]] ? 1u : 0u));
-        st_sys(&r->w[kServeTLoad], tagged_u(tag, (uint32_t)(t_load - t_seen)));
-        st_sys(&r->w[kServeTComp], tagged_u(tag, (uint32_t)(t_comp - t_seen)));
-        st_sys(&r->w[kServeTDone], tagged_u(tag, (uint32_t)(__builtin_amdgcn_s_memrealtime() - t_seen)));
+        const float score = pass_score_word(r, tag, D, se);
+        pass_flag_words(r, tag, score > a.thr[s_model[wid]], t_seen, t_load, t_comp);
       }
     }
     tail += (uint64_t)E;
     passes += 1u;
     events += (uint32_t)E;
     last = __builtin_amdgcn_s_memrealtime();
-    // every wave has issued its result stores and is done with s_xn / s_model / s_ctl before the next poll
-    __syncthreads();
-    if (tid == 0) {
-      st_sys(&ctl->done, tail);   // back-pressure hint only: results carry their own tags
-      st_sys(a.stats, ((uint64_t)passes << 32) | (uint64_t)events);
-    }
+    pass_done(ctl, a.stats, tail, passes, events, tid);
   }
-  __syncthreads();
-  wait_stores();
-  if (tid == 0) st_sys32(&ctl->alive, 0u);
+  pass_exit(ctl, tid);
 }
 
 }  // namespace
@@ -287,7 +240,7 @@ hipError_t dense_fleet_serve_launch(const DenseFleetServeArgs& args, hipStream_t
   if (dense_fleet_serve_check(args.L, args.nl, args.D, args.img_floats, args.stride, args.n_models)[0] ||
       args.nslots < 64 || !args.img || !args.thr || !args.stats)
     return hipErrorInvalidValue;
-  const size_t lds = (size_t)LDS_FLOATS * 4;
+  const size_t lds = (size_t)FIXED_FLOATS * 4;
   const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(dense_serve_fleet_kernel),
                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if (e != hipSuccess) return e;

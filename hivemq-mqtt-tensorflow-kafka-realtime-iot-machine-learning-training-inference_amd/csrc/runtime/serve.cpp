@@ -27,6 +27,41 @@ inline void cpu_relax() {
 
 }  // namespace
 
+DeviceBuffer::DeviceBuffer(size_t bytes, const void* host, const char* what) {
+  ck(hipMalloc(&p_, bytes), (std::string("hipMalloc ") + what).c_str());
+  if (host) ck(hipMemcpy(p_, host, bytes, hipMemcpyHostToDevice), (std::string("copy ") + what).c_str());
+}
+
+DeviceBuffer::~DeviceBuffer() {
+  if (p_) (void)hipFree(p_);
+}
+
+DeviceBuffer& DeviceBuffer::operator=(DeviceBuffer&& o) noexcept {
+  std::swap(p_, o.p_);
+  return *this;
+}
+
+ServeStats::ServeStats() {
+  ck(hipHostMalloc((void**)&host_, 128, hipHostMallocMapped | hipHostMallocCoherent), "hipHostMalloc stats");
+  std::memset(host_, 0, 128);
+  ck(hipHostGetDevicePointer((void**)&dev_, host_, 0), "device ptr stats");
+}
+
+ServeStats::~ServeStats() {
+  if (host_) (void)hipHostFree(host_);
+}
+
+uint64_t ServeStats::read(uint64_t events) const {
+  const uint32_t want = (uint32_t)events;
+  const auto t0 = std::chrono::steady_clock::now();
+  uint64_t v = load_acq(host_);
+  while ((uint32_t)v != want && std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() < 0.5) {
+    cpu_relax();
+    v = load_acq(host_);
+  }
+  return v;
+}
+
 ServeRing::ServeRing(int device, int nslots, int D, double idle_seconds, int max_D, int lanes)
     : device_(device), nslots_(nslots), D_(D), lanes_(lanes), idle_s_(idle_seconds) {
   if (nslots < 64) throw std::invalid_argument("serve: nslots must be >= 64");
@@ -69,6 +104,43 @@ void ServeRing::launch() {
   ++launches_;
 }
 
+void ServeRing::halt() {
+  stop();
+  const auto t0 = std::chrono::steady_clock::now();
+  while (__atomic_load_n(&ctl_->alive, __ATOMIC_ACQUIRE) != 0) {   // stored last by the leaving kernel
+    cpu_relax();
+    if (std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > 10.0)
+      throw std::runtime_error(std::string(name_) + ": the resident kernel did not leave");
+  }
+}
+
+void ServeRing::check_affine(const std::vector<float>& scale, const std::vector<float>& shift, int D, const char* who) {
+  if (!scale.empty() && ((int)scale.size() != D || (int)shift.size() != D))
+    throw std::invalid_argument(std::string(who) + ": scale/shift size");
+}
+
+void ServeRing::upload_affine(const std::vector<float>& scale, const std::vector<float>& shift, const char* who) {
+  check_affine(scale, shift, D_, who);
+  if (scale.empty()) return;
+  scale_d_ = DeviceBuffer(D_ * sizeof(float), scale.data(), "scale");
+  shift_d_ = DeviceBuffer(D_ * sizeof(float), shift.data(), "shift");
+}
+
+template <class Args>
+void ServeRing::fill_dense_args(Args& a, const std::vector<DenseServeLayer>& layers, const ServeStats& stats) const {
+  a.nslots = nslots_;
+  a.D = D_;
+  a.nl = (int)layers.size();
+  for (size_t i = 0; i < layers.size(); ++i) a.L[i] = layers[i];
+  a.idle_ticks = (uint64_t)(idle_s_ * 100e6);   // s_memrealtime runs at 100 MHz
+  a.stats = stats.device();
+  a.ctl = ctl_d_;
+  a.req = req_d_;
+  a.res = res_d_;
+  a.scale = scale_d_.as<float>();
+  a.shift = shift_d_.as<float>();
+}
+
 AEServe::AEServe(int device, int nslots, const std::vector<float>& weights, const int dims[3], const int acts[4],
                  const std::vector<float>& scale, const std::vector<float>& shift, float threshold,
                  double idle_seconds)
@@ -81,31 +153,14 @@ AEServe::AEServe(int device, int nslots, const std::vector<float>& weights, cons
     throw std::invalid_argument("AEServe: dims exceed the serving kernel (D <= 32, hidden <= 16)");
   const size_t nw = (size_t)D * n1 + n1 + (size_t)n1 * n2 + n2 + (size_t)n2 * n2 + n2 + (size_t)n2 * D + D;
   if (weights.size() != nw) throw std::invalid_argument("AEServe: weight vector has the wrong length");
-  ck(hipMalloc((void**)&wts_d_, nw * sizeof(float)), "hipMalloc weights");
-  ck(hipMemcpy(wts_d_, weights.data(), nw * sizeof(float), hipMemcpyHostToDevice), "copy weights");
-  if (!scale.empty()) {
-    if ((int)scale.size() != D || (int)shift.size() != D) throw std::invalid_argument("AEServe: scale/shift size");
-    ck(hipMalloc((void**)&scale_d_, D * sizeof(float)), "hipMalloc scale");
-    ck(hipMalloc((void**)&shift_d_, D * sizeof(float)), "hipMalloc shift");
-    ck(hipMemcpy(scale_d_, scale.data(), D * sizeof(float), hipMemcpyHostToDevice), "copy scale");
-    ck(hipMemcpy(shift_d_, shift.data(), D * sizeof(float), hipMemcpyHostToDevice), "copy shift");
-  }
+  wts_d_ = DeviceBuffer(nw * sizeof(float), weights.data(), "weights");
+  upload_affine(scale, shift, "AEServe");
   launch();
 }
 
-AEServe::~AEServe() {
-  try {
-    stop();
-  } catch (...) {
-  }
-  if (wts_d_) (void)hipFree(wts_d_);
-  if (scale_d_) (void)hipFree(scale_d_);
-  if (shift_d_) (void)hipFree(shift_d_);
-}
-
 hipError_t AEServe::launch_kernel() {
-  return ae_serve_launch(ctl_d_, req_d_, res_d_, nslots_, wts_d_, scale_d_, shift_d_, dims_, acts_, threshold_,
-                         idle_s_, stream_);
+  return ae_serve_launch(ctl_d_, req_d_, res_d_, nslots_, wts_d_.as<float>(), scale_d_.as<float>(),
+                         shift_d_.as<float>(), dims_, acts_, threshold_, idle_s_, stream_);
 }
 
 int DenseServe::checked_D(const std::vector<float>& image, const std::vector<DenseServeLayer>& layers, int D,
@@ -114,8 +169,7 @@ int DenseServe::checked_D(const std::vector<float>& image, const std::vector<Den
     throw std::invalid_argument("DenseServe: the stack must have 1..8 Dense layers");
   const char* why = dense_serve_check(layers.data(), (int)layers.size(), D, (int64_t)image.size());
   if (why[0]) throw std::invalid_argument(std::string("DenseServe: ") + why);
-  if (!scale.empty() && ((int)scale.size() != D || (int)shift.size() != D))
-    throw std::invalid_argument("DenseServe: scale/shift size");
+  check_affine(scale, shift, D, "DenseServe");
   return D;
 }
 
@@ -125,60 +179,17 @@ DenseServe::DenseServe(int device, int nslots, const std::vector<float>& image,
     : ServeRing(device, nslots, checked_D(image, layers, D, scale, shift), idle_seconds, 32) {   // no key word: all 32
   name_ = "DenseServe";
   DenseServeArgs& a = args_;
-  a.nslots = nslots_;
-  a.D = D;
-  a.nl = (int)layers.size();
-  for (size_t i = 0; i < layers.size(); ++i) a.L[i] = layers[i];
+  upload_affine(scale, shift, name_);
+  fill_dense_args(a, layers, stats_);
   a.img_floats = (int)image.size();
   a.threshold = threshold;
-  a.idle_ticks = (uint64_t)(idle_seconds * 100e6);   // s_memrealtime runs at 100 MHz
   in_lds_ = dense_serve_in_lds(a.L, a.nl);
-  ck(hipHostMalloc((void**)&stats_, 128, hipHostMallocMapped | hipHostMallocCoherent), "hipHostMalloc stats");
-  std::memset(stats_, 0, 128);
-  ck(hipHostGetDevicePointer((void**)&a.stats, stats_, 0), "device ptr stats");
-  ck(hipMalloc((void**)&img_d_, image.size() * sizeof(float)), "hipMalloc weight image");
-  ck(hipMemcpy(img_d_, image.data(), image.size() * sizeof(float), hipMemcpyHostToDevice), "copy weight image");
-  if (!scale.empty()) {
-    ck(hipMalloc((void**)&scale_d_, D * sizeof(float)), "hipMalloc scale");
-    ck(hipMalloc((void**)&shift_d_, D * sizeof(float)), "hipMalloc shift");
-    ck(hipMemcpy(scale_d_, scale.data(), D * sizeof(float), hipMemcpyHostToDevice), "copy scale");
-    ck(hipMemcpy(shift_d_, shift.data(), D * sizeof(float), hipMemcpyHostToDevice), "copy shift");
-  }
-  a.ctl = ctl_d_;
-  a.req = req_d_;
-  a.res = res_d_;
-  a.img = img_d_;
-  a.scale = scale_d_;
-  a.shift = shift_d_;
+  img_d_ = DeviceBuffer(image.size() * sizeof(float), image.data(), "weight image");
+  a.img = img_d_.as<float>();
   launch();
 }
 
-DenseServe::~DenseServe() {
-  try {
-    stop();
-  } catch (...) {
-  }
-  if (img_d_) (void)hipFree(img_d_);
-  if (scale_d_) (void)hipFree(scale_d_);
-  if (shift_d_) (void)hipFree(shift_d_);
-  if (stats_) (void)hipHostFree(stats_);
-}
-
 hipError_t DenseServe::launch_kernel() { return dense_serve_launch(args_, stream_); }
-
-uint64_t DenseServe::stats() const {
-  // the kernel stores the word after the pass's result words, which is what wait() polls: a
-  // call can return a moment before the word lands.  Bounded wait until it covers every event
-  // the host has gathered.
-  const uint32_t want = (uint32_t)complete_[0];
-  const auto t0 = std::chrono::steady_clock::now();
-  uint64_t v = load_acq(stats_);
-  while ((uint32_t)v != want && std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() < 0.5) {
-    cpu_relax();
-    v = load_acq(stats_);
-  }
-  return v;
-}
 
 int DenseFleetServe::checked_D(const float* images, int64_t n_models, int64_t stride, int64_t img_floats,
                                const std::vector<DenseServeLayer>& layers, int D, const std::vector<float>& scale,
@@ -189,8 +200,7 @@ int DenseFleetServe::checked_D(const float* images, int64_t n_models, int64_t st
   if (why[0]) throw std::invalid_argument(std::string("DenseFleetServe: ") + why);
   if (!images) throw std::invalid_argument("DenseFleetServe: no images");
   if ((int64_t)thresholds.size() != n_models) throw std::invalid_argument("DenseFleetServe: one threshold per model");
-  if (!scale.empty() && ((int)scale.size() != D || (int)shift.size() != D))
-    throw std::invalid_argument("DenseFleetServe: scale/shift size");
+  check_affine(scale, shift, D, "DenseFleetServe");
   return D;
 }
 
@@ -203,64 +213,19 @@ DenseFleetServe::DenseFleetServe(int device, int nslots, const float* images, in
                 idle_seconds, DSV_FLEET_MAXD) {
   name_ = "DenseFleetServe";
   DenseFleetServeArgs& a = args_;
-  a.nslots = nslots_;
-  a.D = D;
-  a.nl = (int)layers.size();
-  for (size_t i = 0; i < layers.size(); ++i) a.L[i] = layers[i];
+  upload_affine(scale, shift, name_);
+  fill_dense_args(a, layers, stats_);
   a.img_floats = (int)img_floats;
   a.stride = (int)stride;
   a.n_models = (int)n_models;
-  a.idle_ticks = (uint64_t)(idle_seconds * 100e6);   // s_memrealtime runs at 100 MHz
-  ck(hipHostMalloc((void**)&stats_, 128, hipHostMallocMapped | hipHostMallocCoherent), "hipHostMalloc stats");
-  std::memset(stats_, 0, 128);
-  ck(hipHostGetDevicePointer((void**)&a.stats, stats_, 0), "device ptr stats");
-  const size_t nimg = (size_t)n_models * (size_t)stride;
-  ck(hipMalloc((void**)&img_d_, nimg * sizeof(float)), "hipMalloc weight images");
-  ck(hipMemcpy(img_d_, images, nimg * sizeof(float), hipMemcpyHostToDevice), "copy weight images");
-  ck(hipMalloc((void**)&thr_d_, (size_t)n_models * sizeof(float)), "hipMalloc thresholds");
-  ck(hipMemcpy(thr_d_, thresholds.data(), (size_t)n_models * sizeof(float), hipMemcpyHostToDevice),
-     "copy thresholds");
-  if (!scale.empty()) {
-    ck(hipMalloc((void**)&scale_d_, D * sizeof(float)), "hipMalloc scale");
-    ck(hipMalloc((void**)&shift_d_, D * sizeof(float)), "hipMalloc shift");
-    ck(hipMemcpy(scale_d_, scale.data(), D * sizeof(float), hipMemcpyHostToDevice), "copy scale");
-    ck(hipMemcpy(shift_d_, shift.data(), D * sizeof(float), hipMemcpyHostToDevice), "copy shift");
-  }
-  a.ctl = ctl_d_;
-  a.req = req_d_;
-  a.res = res_d_;
-  a.img = img_d_;
-  a.thr = thr_d_;
-  a.scale = scale_d_;
-  a.shift = shift_d_;
+  img_d_ = DeviceBuffer((size_t)n_models * (size_t)stride * sizeof(float), images, "weight images");
+  thr_d_ = DeviceBuffer((size_t)n_models * sizeof(float), thresholds.data(), "thresholds");
+  a.img = img_d_.as<float>();
+  a.thr = thr_d_.as<float>();
   launch();
 }
 
-DenseFleetServe::~DenseFleetServe() {
-  try {
-    stop();
-  } catch (...) {
-  }
-  if (img_d_) (void)hipFree(img_d_);
-  if (thr_d_) (void)hipFree(thr_d_);
-  if (scale_d_) (void)hipFree(scale_d_);
-  if (shift_d_) (void)hipFree(shift_d_);
-  if (stats_) (void)hipHostFree(stats_);
-}
-
 hipError_t DenseFleetServe::launch_kernel() { return dense_fleet_serve_launch(args_, stream_); }
-
-uint64_t DenseFleetServe::stats() const {
-  // as DenseServe::stats: the word lands a moment after the result words wait() polls
-  const uint32_t want = (uint32_t)complete_[0];
-  const auto t0 = std::chrono::steady_clock::now();
-  uint64_t v = load_acq(stats_);
-  while ((uint32_t)v != want && std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() < 0.5) {
-    cpu_relax();
-    v = load_acq(stats_);
-  }
-  return v;
-}
 
 int64_t DenseFleetServe::first_bad_index(const uint32_t* models, int64_t k) const {
   const uint32_t M = (uint32_t)args_.n_models;
@@ -280,25 +245,13 @@ void DenseFleetServe::infer(const float* rows, const uint32_t* models, int k, fl
   ServeRing::infer(rows, k, scores, flags, recon, timeout_s, models);
 }
 
-void DenseFleetServe::halt() {
-  // the resident kernel reads the images: stop it (flag + drain the stream) as LSTMServe::reset_keys
-  // does, so the copy never queues behind a kernel that only leaves at its idle timeout
-  stop();
-  const auto t0 = std::chrono::steady_clock::now();
-  while (__atomic_load_n(&ctl_->alive, __ATOMIC_ACQUIRE) != 0) {   // stored last by the leaving kernel
-    cpu_relax();
-    if (std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > 10.0)
-      throw std::runtime_error("DenseFleetServe: the resident kernel did not leave");
-  }
-}
-
 void DenseFleetServe::set_image(int64_t i, const float* image) {
   if (i < 0 || i >= (int64_t)args_.n_models)
     throw std::invalid_argument("DenseFleetServe: model index " + std::to_string(i) + " is outside [0, " +
                                 std::to_string(args_.n_models) + ")");
   halt();
   ck(hipSetDevice(device_), "hipSetDevice");
-  ck(hipMemcpy(img_d_ + (size_t)i * (size_t)args_.stride, image, (size_t)args_.stride * sizeof(float),
+  ck(hipMemcpy(img_d_.as<float>() + (size_t)i * (size_t)args_.stride, image, (size_t)args_.stride * sizeof(float),
                hipMemcpyHostToDevice),
      "copy weight image");
 }
@@ -306,7 +259,8 @@ void DenseFleetServe::set_image(int64_t i, const float* image) {
 void DenseFleetServe::set_images(const float* images) {
   halt();
   ck(hipSetDevice(device_), "hipSetDevice");
-  ck(hipMemcpy(img_d_, images, (size_t)args_.n_models * (size_t)args_.stride * sizeof(float), hipMemcpyHostToDevice),
+  ck(hipMemcpy(img_d_.as<float>(), images, (size_t)args_.n_models * (size_t)args_.stride * sizeof(float),
+               hipMemcpyHostToDevice),
      "copy weight images");
 }
 
@@ -351,8 +305,7 @@ LSTMServe::LSTMServe(int device, int nslots, const std::vector<float>& weights,
         (L.kind == LS_LSTM && (L.uoff < 0 || (int64_t)L.uoff + (int64_t)L.u * G > (int64_t)weights.size())))
       throw std::invalid_argument("LSTMServe: a layer's weights lie outside the weight vector");
   }
-  if (!scale.empty() && ((int)scale.size() != D || (int)shift.size() != D))
-    throw std::invalid_argument("LSTMServe: scale/shift size");
+  check_affine(scale, shift, D, "LSTMServe");
   LstmServeArgs& a = args_;
   a.nslots = nslots_;
   a.lanes = lanes_;
@@ -376,24 +329,21 @@ LSTMServe::LSTMServe(int device, int nslots, const std::vector<float>& weights,
   } else if (lstm_serve_lds_bytes((int)weights.size()) > 160 * 1024) {
     throw std::invalid_argument("LSTMServe: the weights do not fit the scorer's LDS");
   }
-  ck(hipMalloc((void**)&wts_d_, weights.size() * sizeof(float)), "hipMalloc weights");
-  ck(hipMemcpy(wts_d_, weights.data(), weights.size() * sizeof(float), hipMemcpyHostToDevice), "copy weights");
-  if (!scale.empty()) {
-    ck(hipMalloc((void**)&scale_d_, D * sizeof(float)), "hipMalloc scale");
-    ck(hipMalloc((void**)&shift_d_, D * sizeof(float)), "hipMalloc shift");
-    ck(hipMemcpy(scale_d_, scale.data(), D * sizeof(float), hipMemcpyHostToDevice), "copy scale");
-    ck(hipMemcpy(shift_d_, shift.data(), D * sizeof(float), hipMemcpyHostToDevice), "copy shift");
-  }
+  wts_d_ = DeviceBuffer(weights.size() * sizeof(float), weights.data(), "weights");
+  upload_affine(scale, shift, name_);
   a.ctl = ctl_d_;
   a.req = req_d_;
   a.res = res_d_;
-  a.wts = wts_d_;
-  a.scale = scale_d_;
-  a.shift = shift_d_;
+  a.wts = wts_d_.as<float>();
+  a.scale = scale_d_.as<float>();
+  a.shift = shift_d_.as<float>();
   if (kernel_ == LSK_WIDE) build_wide(weights);
-  ck(hipMalloc((void**)&a.hist, (size_t)nkeys * T * D * sizeof(float)), "hipMalloc windows");
-  ck(hipMalloc((void**)&a.hcount, (size_t)nkeys * sizeof(int)), "hipMalloc counts");
-  ck(hipMalloc((void**)&a.lastpred, (size_t)nkeys * D * sizeof(float)), "hipMalloc forecasts");
+  hist_d_ = DeviceBuffer((size_t)nkeys * T * D * sizeof(float), nullptr, "windows");
+  hcount_d_ = DeviceBuffer((size_t)nkeys * sizeof(int), nullptr, "counts");
+  lastpred_d_ = DeviceBuffer((size_t)nkeys * D * sizeof(float), nullptr, "forecasts");
+  a.hist = hist_d_.as<float>();
+  a.hcount = hcount_d_.as<int>();
+  a.lastpred = lastpred_d_.as<float>();
   reset_keys();   // zeroes the key state and launches the resident kernel
 }
 
@@ -431,17 +381,19 @@ void LSTMServe::build_wide(const std::vector<float>& weights) {
       for (int j = 0; j < L.u; ++j) b[q * up + j] = weights[(size_t)L.boff + q * L.u + j];
     ++li;
   }
-  ck(hipMalloc(&wide_d_, total), "hipMalloc weight images");
-  ck(hipMemcpyAsync(wide_d_, img.data(), total, hipMemcpyHostToDevice, stream_), "copy weight images");
+  wide_d_ = DeviceBuffer(total, nullptr, "weight images");
+  unsigned char* const wide = wide_d_.as<unsigned char>();
+  ck(hipMemcpyAsync(wide, img.data(), total, hipMemcpyHostToDevice, stream_), "copy weight images");
   ck(hipStreamSynchronize(stream_), "sync");
   for (int i = 0; i < li; ++i) {
-    a.wide_w[i] = reinterpret_cast<const uint16_t*>(static_cast<unsigned char*>(wide_d_) + off[i][0]);
-    a.wide_u[i] = reinterpret_cast<const uint16_t*>(static_cast<unsigned char*>(wide_d_) + off[i][1]);
-    a.wide_b[i] = reinterpret_cast<const float*>(static_cast<unsigned char*>(wide_d_) + off[i][2]);
+    a.wide_w[i] = reinterpret_cast<const uint16_t*>(wide + off[i][0]);
+    a.wide_u[i] = reinterpret_cast<const uint16_t*>(wide + off[i][1]);
+    a.wide_b[i] = reinterpret_cast<const float*>(wide + off[i][2]);
   }
   const LstmServeWideDims d = lstm_serve_wide_dims(a);
-  ck(hipMalloc((void**)&a.wide_zx, (size_t)lanes_ * d.rows * d.gmax * sizeof(float)),   // one scratch per lane
-     "hipMalloc projection scratch");
+  wide_zx_d_ = DeviceBuffer((size_t)lanes_ * d.rows * d.gmax * sizeof(float), nullptr,   // one scratch per lane
+                            "projection scratch");
+  a.wide_zx = wide_zx_d_.as<float>();
 }
 
 const char* LSTMServe::kernel() const {
@@ -458,21 +410,6 @@ void LSTMServe::reset_keys() {
   ck(hipMemsetAsync(args_.lastpred, 0, (size_t)args_.nkeys * args_.D * sizeof(float), stream_), "memset forecasts");
   ck(hipStreamSynchronize(stream_), "sync");
   launch();
-}
-
-LSTMServe::~LSTMServe() {
-  try {
-    stop();
-  } catch (...) {
-  }
-  if (wide_d_) (void)hipFree(wide_d_);
-  if (args_.wide_zx) (void)hipFree(args_.wide_zx);
-  if (args_.hist) (void)hipFree(args_.hist);
-  if (args_.hcount) (void)hipFree(args_.hcount);
-  if (args_.lastpred) (void)hipFree(args_.lastpred);
-  if (wts_d_) (void)hipFree(wts_d_);
-  if (scale_d_) (void)hipFree(scale_d_);
-  if (shift_d_) (void)hipFree(shift_d_);
 }
 
 hipError_t LSTMServe::launch_kernel() { return lstm_serve_launch(args_, stream_); }

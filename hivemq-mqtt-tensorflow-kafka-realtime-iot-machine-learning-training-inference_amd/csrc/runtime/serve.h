@@ -25,6 +25,40 @@
 
 namespace sml {
 
+// A device allocation that frees itself (move-only).
+class DeviceBuffer {
+ public:
+  DeviceBuffer() = default;
+  // bytes on the current device, filled from host unless it is null; what: names it in an error
+  DeviceBuffer(size_t bytes, const void* host, const char* what);
+  ~DeviceBuffer();
+  DeviceBuffer(DeviceBuffer&& o) noexcept : p_(o.p_) { o.p_ = nullptr; }
+  DeviceBuffer& operator=(DeviceBuffer&& o) noexcept;
+  template <class T>
+  T* as() const { return static_cast<T*>(p_); }
+
+ private:
+  void* p_ = nullptr;
+};
+
+// The Dense scorers' stats block: 128 host-mapped, coherent bytes whose first word the kernel stores
+// after each pass, {passes << 32 | events}, cumulative.
+class ServeStats {
+ public:
+  ServeStats();
+  ~ServeStats();
+  ServeStats(const ServeStats&) = delete;
+  ServeStats& operator=(const ServeStats&) = delete;
+  uint64_t* device() const { return dev_; }
+  // the word, read once it covers `events` events (bounded wait: the kernel stores it a moment after
+  // the result words that the host polls)
+  uint64_t read(uint64_t events) const;
+
+ private:
+  uint64_t* host_ = nullptr;
+  uint64_t* dev_ = nullptr;
+};
+
 // The host-mapped request / result rings and the relaunch-on-demand protocol shared by the
 // persistent scorers; a subclass supplies the kernel launch.
 class ServeRing {
@@ -77,6 +111,17 @@ class ServeRing {
   // back-pressure: block until the device consumed every event < n (its request slot is free)
   void wait_done(uint64_t n, double timeout_s, int lane = 0);
   void mark_lane_events();   // lane_events() counts from here
+  // stop the resident kernel and wait until it has left (alive == 0): what a copy into memory the
+  // kernel reads needs, so that it never queues behind a kernel that only leaves at its idle timeout
+  void halt();
+  // the optional input normaliser: both empty, or D entries each (else invalid_argument "<who>:
+  // scale/shift size"); upload_affine fills scale_d_ / shift_d_
+  static void check_affine(const std::vector<float>& scale, const std::vector<float>& shift, int D, const char* who);
+  void upload_affine(const std::vector<float>& scale, const std::vector<float>& shift, const char* who);
+  // the front both Dense scorers' argument structs share (rings, D, layer table, normaliser, idle
+  // ticks, stats word); the structs stay two: their layout is part of the kernels
+  template <class Args>
+  void fill_dense_args(Args& a, const std::vector<DenseServeLayer>& layers, const ServeStats& stats) const;
   int device_, nslots_, D_, lanes_;
   double idle_s_;
   ServeCtl* ctl_ = nullptr;      // [lanes]
@@ -86,6 +131,7 @@ class ServeRing {
   ServeReq* req_d_ = nullptr;
   ServeResult* res_d_ = nullptr;
   hipStream_t stream_ = nullptr;
+  DeviceBuffer scale_d_, shift_d_;   // [D] each, or empty
   std::vector<uint64_t> head_;       // per lane: events published
   std::vector<uint64_t> complete_;   // per lane: events known complete (prefix)
   std::vector<uint64_t> done0_;      // per lane: `done` at mark_lane_events()
@@ -109,7 +155,7 @@ class AEServe : public ServeRing {
  public:
   AEServe(int device, int nslots, const std::vector<float>& weights, const int dims[3], const int acts[4],
           const std::vector<float>& scale, const std::vector<float>& shift, float threshold, double idle_seconds);
-  ~AEServe() override;
+  ~AEServe() override { stop(); }   // before any member frees its buffer
 
  protected:
   hipError_t launch_kernel() override;
@@ -117,9 +163,7 @@ class AEServe : public ServeRing {
  private:
   int dims_[3], acts_[4];
   float threshold_;
-  float* wts_d_ = nullptr;
-  float* scale_d_ = nullptr;
-  float* shift_d_ = nullptr;
+  DeviceBuffer wts_d_;
 };
 
 // Dense stacks of any depth (dense_serve.hip): 1..8 Dense layers up to 512 wide, rows of up to
@@ -130,13 +174,13 @@ class DenseServe : public ServeRing {
   DenseServe(int device, int nslots, const std::vector<float>& image, const std::vector<DenseServeLayer>& layers,
              int D, const std::vector<float>& scale, const std::vector<float>& shift, float threshold,
              double idle_seconds);
-  ~DenseServe() override;
+  ~DenseServe() override { stop(); }   // before any member frees its buffer
   // where the resident kernel keeps the image: "lds" | "stream"
   const char* kernel() const { return in_lds_ ? "lds" : "stream"; }
   // passes the kernel ran and events they served since construction (its stats word, read once
   // it covers every event this host has gathered)
-  uint64_t passes() const { return stats() >> 32; }
-  uint64_t events() const { return stats() & 0xffffffffull; }
+  uint64_t passes() const { return stats_.read(complete_[0]) >> 32; }
+  uint64_t events() const { return stats_.read(complete_[0]) & 0xffffffffull; }
 
  protected:
   hipError_t launch_kernel() override;
@@ -145,13 +189,10 @@ class DenseServe : public ServeRing {
   // every limit, before the base class allocates the rings; returns D
   static int checked_D(const std::vector<float>& image, const std::vector<DenseServeLayer>& layers, int D,
                        const std::vector<float>& scale, const std::vector<float>& shift);
-  uint64_t stats() const;
   DenseServeArgs args_{};
   bool in_lds_ = false;
-  uint64_t* stats_ = nullptr;   // host-mapped, 128 bytes
-  float* img_d_ = nullptr;
-  float* scale_d_ = nullptr;
-  float* shift_d_ = nullptr;
+  ServeStats stats_;
+  DeviceBuffer img_d_;
 };
 
 // A fleet of Dense stacks of one shape (dense_serve_fleet.hip): every event names the model that
@@ -165,12 +206,12 @@ class DenseFleetServe : public ServeRing {
   DenseFleetServe(int device, int nslots, const float* images, int64_t n_models, int64_t stride, int64_t img_floats,
                   const std::vector<DenseServeLayer>& layers, int D, const std::vector<float>& scale,
                   const std::vector<float>& shift, const std::vector<float>& thresholds, double idle_seconds);
-  ~DenseFleetServe() override;
+  ~DenseFleetServe() override { stop(); }   // before any member frees its buffer
   int64_t n_models() const { return args_.n_models; }
   int64_t stride() const { return args_.stride; }
   const char* kernel() const { return "fleet"; }
-  uint64_t passes() const { return stats() >> 32; }
-  uint64_t events() const { return stats() & 0xffffffffull; }
+  uint64_t passes() const { return stats_.read(complete_[0]) >> 32; }
+  uint64_t events() const { return stats_.read(complete_[0]) & 0xffffffffull; }
   // submit + wait + copy for k rows, row i scored by model models[i].  Every index is checked
   // before anything is published: std::invalid_argument names the first one >= n_models.
   void infer(const float* rows, const uint32_t* models, int k, float* scores, uint32_t* flags, float* recon,
@@ -189,14 +230,9 @@ class DenseFleetServe : public ServeRing {
   static int checked_D(const float* images, int64_t n_models, int64_t stride, int64_t img_floats,
                        const std::vector<DenseServeLayer>& layers, int D, const std::vector<float>& scale,
                        const std::vector<float>& shift, const std::vector<float>& thresholds);
-  uint64_t stats() const;
-  void halt();   // stop the resident kernel, wait for alive == 0
   DenseFleetServeArgs args_{};
-  uint64_t* stats_ = nullptr;   // host-mapped, 128 bytes
-  float* img_d_ = nullptr;
-  float* thr_d_ = nullptr;
-  float* scale_d_ = nullptr;
-  float* shift_d_ = nullptr;
+  ServeStats stats_;
+  DeviceBuffer img_d_, thr_d_;
 };
 
 // LSTM forecaster (lstm_serve.hip): per car key, the last T events stay on the device; each
@@ -209,7 +245,7 @@ class LSTMServe : public ServeRing {
   LSTMServe(int device, int nslots, const std::vector<float>& weights, const std::vector<LstmServeLayer>& layers,
             int D, int T, int nkeys, const std::vector<float>& scale, const std::vector<float>& shift, float threshold,
             double idle_seconds, int lanes = 1);
-  ~LSTMServe() override;
+  ~LSTMServe() override { stop(); }   // before any member frees its buffer
   int nkeys() const { return args_.nkeys; }
   // forget every key's window and forecast: stops the resident kernel, zeroes the key state
   // on the device, relaunches (returns without waiting for the kernel's idle timeout)
@@ -228,10 +264,8 @@ class LSTMServe : public ServeRing {
   void build_wide(const std::vector<float>& weights);
   LstmServeArgs args_{};
   int kernel_ = LSK_GENERIC;
-  void* wide_d_ = nullptr;
-  float* wts_d_ = nullptr;
-  float* scale_d_ = nullptr;
-  float* shift_d_ = nullptr;
+  DeviceBuffer wts_d_, wide_d_, wide_zx_d_;
+  DeviceBuffer hist_d_, hcount_d_, lastpred_d_;   // the key state
 };
 
 }  // namespace sml

@@ -1493,8 +1493,29 @@ struct RingPy {
 // Python face of the persistent scorer: numpy in / numpy out, GIL released while
 // the host thread spins on the completion counter.
 struct ServePy {
+  using farray = py::array_t<float, py::array::c_style | py::array::forcecast>;
   std::unique_ptr<sml::ServeRing> s;
   ServePy() = default;
+  // the optional normaliser arrays -> (scale, shift), both empty for None
+  static std::pair<std::vector<float>, std::vector<float>> affine_of(const py::object& scale, const py::object& shift) {
+    std::vector<float> sc, sh;
+    if (!scale.is_none()) {
+      auto a = scale.cast<farray>();
+      auto b = shift.cast<farray>();
+      sc.assign(a.data(), a.data() + a.size());
+      sh.assign(b.data(), b.data() + b.size());
+    }
+    return {sc, sh};
+  }
+  // list of (in, out, act, w_off, b_off) rows -> the Dense scorers' layer table
+  static std::vector<sml::DenseServeLayer> dense_layers_of(const std::vector<std::vector<int>>& layers) {
+    std::vector<sml::DenseServeLayer> L;
+    for (const auto& t : layers) {
+      if (t.size() != 5) throw std::invalid_argument("layer descriptor: (in, out, act, w_off, b_off)");
+      L.push_back(sml::DenseServeLayer{t[0], t[1], t[2], t[3], t[4]});
+    }
+    return L;
+  }
   // C ABI for the host-only streaming loop in _io (sml_scorer_api.h)
   SmlScorerApi api{};
   std::string err;
@@ -1550,13 +1571,7 @@ struct ServePy {
           double idle_seconds) {
     if (dims.size() != 3 || acts.size() != 4) throw std::invalid_argument("dims = [D, n1, n2], acts = 4 codes");
     std::vector<float> w(weights.data(), weights.data() + weights.size());
-    std::vector<float> sc, sh;
-    if (!scale.is_none()) {
-      auto a = scale.cast<py::array_t<float, py::array::c_style | py::array::forcecast>>();
-      auto b = shift.cast<py::array_t<float, py::array::c_style | py::array::forcecast>>();
-      sc.assign(a.data(), a.data() + a.size());
-      sh.assign(b.data(), b.data() + b.size());
-    }
+    const auto [sc, sh] = affine_of(scale, shift);
     c10::hip::HIPGuard guard(device);
     s = std::make_unique<sml::AEServe>(device, nslots, w, dims.data(), acts.data(), sc, sh, (float)threshold,
                                        idle_seconds);
@@ -1633,13 +1648,7 @@ struct LSTMServePy : ServePy {
       if (t.size() != 9) throw std::invalid_argument("layer descriptor: (kind, in, u, act, ret, n, woff, uoff, boff)");
       L.push_back(sml::LstmServeLayer{t[0], t[1], t[2], t[3], t[4], t[5], t[6], t[7], t[8]});
     }
-    std::vector<float> sc, sh;
-    if (!scale.is_none()) {
-      auto a = scale.cast<py::array_t<float, py::array::c_style | py::array::forcecast>>();
-      auto b = shift.cast<py::array_t<float, py::array::c_style | py::array::forcecast>>();
-      sc.assign(a.data(), a.data() + a.size());
-      sh.assign(b.data(), b.data() + b.size());
-    }
+    const auto [sc, sh] = affine_of(scale, shift);
     c10::hip::HIPGuard guard(device);
     s = std::make_unique<sml::LSTMServe>(device, nslots, w, L, D, T, nkeys, sc, sh, (float)threshold, idle_seconds,
                                          lanes);
@@ -1655,18 +1664,8 @@ struct DenseServePy : ServePy {
                std::vector<std::vector<int>> layers, int D, py::object scale, py::object shift, double threshold,
                double idle_seconds) {
     std::vector<float> img(image.data(), image.data() + image.size());
-    std::vector<sml::DenseServeLayer> L;
-    for (const auto& t : layers) {
-      if (t.size() != 5) throw std::invalid_argument("layer descriptor: (in, out, act, w_off, b_off)");
-      L.push_back(sml::DenseServeLayer{t[0], t[1], t[2], t[3], t[4]});
-    }
-    std::vector<float> sc, sh;
-    if (!scale.is_none()) {
-      auto a = scale.cast<py::array_t<float, py::array::c_style | py::array::forcecast>>();
-      auto b = shift.cast<py::array_t<float, py::array::c_style | py::array::forcecast>>();
-      sc.assign(a.data(), a.data() + a.size());
-      sh.assign(b.data(), b.data() + b.size());
-    }
+    const std::vector<sml::DenseServeLayer> L = dense_layers_of(layers);
+    const auto [sc, sh] = affine_of(scale, shift);
     c10::hip::HIPGuard guard(device);
     s = std::make_unique<sml::DenseServe>(device, nslots, img, L, D, sc, sh, (float)threshold, idle_seconds);
   }
@@ -1677,22 +1676,11 @@ struct DenseServePy : ServePy {
 // tuples, offsets relative to a model's image; thresholds: [M].  Keyed by the model index:
 // _io.ScoreLoop drives it through c_api()'s infer_keyed with nkeys = M.
 struct DenseFleetServePy : ServePy {
-  using farray = py::array_t<float, py::array::c_style | py::array::forcecast>;
   DenseFleetServePy(int device, int nslots, farray images, int64_t img_floats, std::vector<std::vector<int>> layers,
                     int D, py::object scale, py::object shift, farray thresholds, double idle_seconds) {
     if (images.ndim() != 2) throw std::invalid_argument("images must be [M, stride]");
-    std::vector<sml::DenseServeLayer> L;
-    for (const auto& t : layers) {
-      if (t.size() != 5) throw std::invalid_argument("layer descriptor: (in, out, act, w_off, b_off)");
-      L.push_back(sml::DenseServeLayer{t[0], t[1], t[2], t[3], t[4]});
-    }
-    std::vector<float> sc, sh;
-    if (!scale.is_none()) {
-      auto a = scale.cast<farray>();
-      auto b = shift.cast<farray>();
-      sc.assign(a.data(), a.data() + a.size());
-      sh.assign(b.data(), b.data() + b.size());
-    }
+    const std::vector<sml::DenseServeLayer> L = dense_layers_of(layers);
+    const auto [sc, sh] = affine_of(scale, shift);
     std::vector<float> thr(thresholds.data(), thresholds.data() + thresholds.size());
     c10::hip::HIPGuard guard(device);
     s = std::make_unique<sml::DenseFleetServe>(device, nslots, images.data(), (int64_t)images.shape(0),

@@ -32,7 +32,83 @@ import torch
 from ._ext import load_c
 
 
-class ScoringServer:
+class _Server:
+    """What the scoring servers share: the life of the native server ``_s`` (``close`` tolerates an
+    object whose construction failed before ``_s`` was set) and the columns of a latency run."""
+
+    @staticmethod
+    def _latency_columns(out, device_breakdown: bool):
+        if device_breakdown:   # (host round trip, device total, device row-load, device compute)
+            return out[:, 0], out[:, 1], out[:, 2], out[:, 3]
+        return out[:, 0]
+
+    @property
+    def launches(self) -> int:
+        return int(self._s.launches)
+
+    def close(self) -> None:
+        if getattr(self, "_s", None) is not None:
+            self._s.stop()
+            self._s = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class _DenseServer(_Server):
+    """The counters both Dense scorers read from their kernel's stats word."""
+
+    @property
+    def kernel(self) -> str:
+        """Where the resident kernel reads the weights: "lds" | "stream", or "fleet" (always, for a
+        fleet: the images stay in device memory)."""
+        return str(self._s.kernel)
+
+    @property
+    def passes(self) -> int:
+        """Passes the kernel ran since construction (one pass serves 1 .. ``MAX_PASS`` events)."""
+        return int(self._s.passes)
+
+    @property
+    def events(self) -> int:
+        """Events those passes served."""
+        return int(self._s.events)
+
+
+def _resolve_normalizer(normalizer, D: int, model, what: str):
+    """(scale, shift) as fp32 ``[D]`` arrays, or (None, None): ``normalizer`` is None (``model``'s own,
+    if it has one), ``"cardata"``, ``"none"`` or a ``(scale, shift)`` pair.  ``what``: "the model has"
+    / "the models have", for the message."""
+    sc = sh = None
+    if normalizer is None:
+        if hasattr(model, "_normalizer"):   # an Autoencoder's own input normaliser
+            sc, sh = model._normalizer()
+    elif isinstance(normalizer, str) and normalizer == "cardata":
+        from ..data.cardata import normalize_affine
+        if D != 18:
+            raise ValueError(f"the cardata normaliser needs 18 features ({what} {D})")
+        sc, sh = normalize_affine()
+    elif not (isinstance(normalizer, str) and normalizer == "none"):
+        if isinstance(normalizer, str) or len(normalizer) != 2:
+            raise ValueError(f"unknown normalizer {normalizer!r}")
+        sc, sh = normalizer
+    if sc is not None:
+        sc, sh = np.asarray(sc, np.float32).reshape(-1), np.asarray(sh, np.float32).reshape(-1)
+        if sc.size != D or sh.size != D:
+            raise ValueError(f"normalizer scale / shift must have {D} entries")
+    return sc, sh
+
+
+class ScoringServer(_Server):
     def __init__(self, model, threshold: float = 5.0, slots: int = 4096, idle_seconds: float = 2.0,
                  device: Optional[torch.device] = None):
         dev = torch.device(device) if device is not None else model.device
@@ -65,30 +141,7 @@ class ScoringServer:
         with ``device_breakdown`` also the on-device processing time of each event (us)."""
         gap = int(1e9 / qps) if qps > 0 else 0
         out = self._s.latency_run(np.ascontiguousarray(np.asarray(rows, np.float32)), gap) / 1e3
-        if device_breakdown:   # (host round trip, device total, device row-load, device compute)
-            return out[:, 0], out[:, 1], out[:, 2], out[:, 3]
-        return out[:, 0]
-
-    @property
-    def launches(self) -> int:
-        return int(self._s.launches)
-
-    def close(self) -> None:
-        if self._s is not None:
-            self._s.stop()
-            self._s = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return self._latency_columns(out, device_breakdown)
 
 
 def dense_layer_table(model) -> Tuple[list, list]:
@@ -128,6 +181,12 @@ def dense_layer_table(model) -> Tuple[list, list]:
 DENSE_SERVE_TILE = 32   # output widths are zero-padded to this, input widths to 4
 
 
+def _dense_image_floats(layers) -> int:
+    """Floats of the packed image of ``layers``: per layer ``Kp * Np`` weights and ``Np`` biases."""
+    t = DENSE_SERVE_TILE
+    return sum(((i + 3) // 4 * 4 + 1) * ((o + t - 1) // t * t) for i, o, _, _ in layers)
+
+
 def dense_serve_image(layers, weights) -> Tuple[np.ndarray, list]:
     """Pack the weight image of ``dense_serve.hip``: per layer ``float4 img[Kp / 4][Np]`` with
     ``img[g][o] = W[4g .. 4g + 3][o]`` (``Kp`` = in rounded up to 4, ``Np`` = units rounded up to
@@ -153,7 +212,7 @@ def dense_serve_image(layers, weights) -> Tuple[np.ndarray, list]:
     return np.ascontiguousarray(image, np.float32), table
 
 
-class DenseScoringServer:
+class DenseScoringServer(_DenseServer):
     """Persistent per-event scorer for a Dense stack of any depth (``dense_serve.hip``): 1 ..
     ``MAX_LAYERS`` Dense layers, every width up to ``MAX_WIDTH``, rows of up to ``MAX_FEATURES``
     features, the last layer one unit per feature.  Same surface and semantics as
@@ -199,9 +258,7 @@ class DenseScoringServer:
     def kernel_for(model) -> str:
         """"lds" | "stream": where the resident kernel will keep the weights of ``model``."""
         layers, _ = dense_layer_table(model)
-        t = DENSE_SERVE_TILE
-        nbytes = sum(4 * (((i + 3) // 4 * 4) * ((o + t - 1) // t * t) + (o + t - 1) // t * t) for i, o, _, _ in layers)
-        return "lds" if nbytes <= DenseScoringServer.LDS_IMAGE_BYTES else "stream"
+        return "lds" if 4 * _dense_image_floats(layers) <= DenseScoringServer.LDS_IMAGE_BYTES else "stream"
 
     def __init__(self, model, threshold: float = 5.0, slots: int = 4096, idle_seconds: float = 2.0,
                  normalizer=None, device: Optional[torch.device] = None):
@@ -214,23 +271,7 @@ class DenseScoringServer:
         layers, weights = dense_layer_table(model)
         image, table = dense_serve_image(layers, weights)
         self.D = int(layers[0][0])
-        sc = sh = None
-        if normalizer is None:
-            if hasattr(model, "_normalizer"):   # an Autoencoder's own input normaliser
-                sc, sh = model._normalizer()
-        elif isinstance(normalizer, str) and normalizer == "cardata":
-            from ..data.cardata import normalize_affine
-            if self.D != 18:
-                raise ValueError(f"the cardata normaliser needs 18 features (the model has {self.D})")
-            sc, sh = normalize_affine()
-        elif not (isinstance(normalizer, str) and normalizer == "none"):
-            if isinstance(normalizer, str) or len(normalizer) != 2:
-                raise ValueError(f"unknown normalizer {normalizer!r}")
-            sc, sh = normalizer
-        if sc is not None:
-            sc, sh = np.asarray(sc, np.float32).reshape(-1), np.asarray(sh, np.float32).reshape(-1)
-            if sc.size != self.D or sh.size != self.D:
-                raise ValueError(f"normalizer scale / shift must have {self.D} entries")
+        sc, sh = _resolve_normalizer(normalizer, self.D, model, "the model has")
         self.threshold = float(threshold)
         C = load_c()
         assert (C.DSV_MAXW, C.DSV_MAXLAYERS, C.DSV_EB, C.DSV_LDS_IMAGE_BYTES) == (
@@ -254,45 +295,7 @@ class DenseScoringServer:
         with ``device_breakdown`` also the on-device processing time of each event (us)."""
         gap = int(1e9 / qps) if qps > 0 else 0
         out = self._s.latency_run(np.ascontiguousarray(np.asarray(rows, np.float32)), gap) / 1e3
-        if device_breakdown:   # (host round trip, device total, device row-load, device compute)
-            return out[:, 0], out[:, 1], out[:, 2], out[:, 3]
-        return out[:, 0]
-
-    @property
-    def kernel(self) -> str:
-        """Where the resident kernel keeps the weight image: "lds" | "stream"."""
-        return str(self._s.kernel)
-
-    @property
-    def passes(self) -> int:
-        """Passes the kernel ran since construction (one pass serves 1 .. ``MAX_PASS`` events)."""
-        return int(self._s.passes)
-
-    @property
-    def events(self) -> int:
-        """Events those passes served."""
-        return int(self._s.events)
-
-    @property
-    def launches(self) -> int:
-        return int(self._s.launches)
-
-    def close(self) -> None:
-        if self._s is not None:
-            self._s.stop()
-            self._s = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return self._latency_columns(out, device_breakdown)
 
 
 def _dense_flat_offsets(layers) -> list:
@@ -339,7 +342,7 @@ def dense_fleet_serve_images(layers, flats_or_weight_lists, offsets=None) -> Tup
     offsets = _dense_flat_offsets(layers) if offsets is None else list(offsets)
     M, t = flats.shape[0], DENSE_SERVE_TILE
     geo = [((i + 3) // 4 * 4, (o + t - 1) // t * t) for i, o, _, _ in layers]
-    img_floats = sum(kp * npad + npad for kp, npad in geo)
+    img_floats = _dense_image_floats(layers)
     stride = (img_floats + 3) // 4 * 4
     images = np.zeros((M, stride), np.float32)
     table, off = [], 0
@@ -357,7 +360,7 @@ def dense_fleet_serve_images(layers, flats_or_weight_lists, offsets=None) -> Tup
     return images, table
 
 
-class DenseFleetScoringServer:
+class DenseFleetScoringServer(_DenseServer):
     """Persistent per-event scorer for a FLEET of Dense stacks of one shape (``dense_serve_fleet.hip``):
     every row names the member that scores it, ``score(rows, models)``.  One resident workgroup holds
     the whole fleet: the members' weight images are stacked in device memory and each event reads its
@@ -445,26 +448,11 @@ class DenseFleetScoringServer:
         if thr.shape != (M,):
             raise ValueError(f"thresholds must be one number or [{M}], one per model")
         self.thresholds = thr
-        sc = sh = None
-        if isinstance(normalizer, str) and normalizer == "cardata":
-            from ..data.cardata import normalize_affine
-            if self.D != 18:
-                raise ValueError(f"the cardata normaliser needs 18 features (the models have {self.D})")
-            sc, sh = normalize_affine()
-        elif normalizer is not None and not (isinstance(normalizer, str) and normalizer == "none"):
-            if isinstance(normalizer, str) or len(normalizer) != 2:
-                raise ValueError(f"unknown normalizer {normalizer!r}")
-            sc, sh = normalizer
-        if sc is not None:
-            sc, sh = np.asarray(sc, np.float32).reshape(-1), np.asarray(sh, np.float32).reshape(-1)
-            if sc.size != self.D or sh.size != self.D:
-                raise ValueError(f"normalizer scale / shift must have {self.D} entries")
+        sc, sh = _resolve_normalizer(normalizer, self.D, None, "the models have")
         C = load_c()
         assert (C.DSV_FLEET_MAXD, C.DSV_FLEET_MAXMODELS - 1) == (self.MAX_FEATURES, self.MAX_MODELS)
-        t = DENSE_SERVE_TILE
-        img_floats = sum(((i + 3) // 4 * 4 + 1) * ((o + t - 1) // t * t) for i, o, _, _ in layers)
         self._s = C.DenseFleetServe(dev.index if dev.index is not None else torch.cuda.current_device(), int(slots),
-                                    np.ascontiguousarray(images, np.float32), int(img_floats),
+                                    np.ascontiguousarray(images, np.float32), _dense_image_floats(layers),
                                     [list(r) for r in table], self.D, sc, sh, thr, float(idle_seconds))
 
     @classmethod
@@ -553,9 +541,7 @@ class DenseFleetScoringServer:
         rows, idx = self._rows_models(rows, models)
         gap = int(1e9 / qps) if qps > 0 else 0
         out = self._s.latency_models(rows, gap, idx) / 1e3
-        if device_breakdown:   # (host round trip, device total, device row-load, device compute)
-            return out[:, 0], out[:, 1], out[:, 2], out[:, 3]
-        return out[:, 0]
+        return self._latency_columns(out, device_breakdown)
 
     def set_weights(self, i: int, weights) -> None:
         """Replace member i's weights (a Keras-order list as ``model.get_weights()`` gives, or the
@@ -588,42 +574,6 @@ class DenseFleetScoringServer:
     def stride(self) -> int:
         """Floats between two members' weight images in device memory."""
         return int(self._s.stride)
-
-    @property
-    def kernel(self) -> str:
-        """Always "fleet": the images stay in device memory."""
-        return str(self._s.kernel)
-
-    @property
-    def passes(self) -> int:
-        """Passes the kernel ran since construction (one pass serves 1 .. ``MAX_PASS`` events)."""
-        return int(self._s.passes)
-
-    @property
-    def events(self) -> int:
-        """Events those passes served."""
-        return int(self._s.events)
-
-    @property
-    def launches(self) -> int:
-        return int(self._s.launches)
-
-    def close(self) -> None:
-        if getattr(self, "_s", None) is not None:
-            self._s.stop()
-            self._s = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def read_fleet_index(path) -> Tuple[list, list, dict]:
@@ -671,7 +621,7 @@ def lstm_layer_table(model) -> Tuple[np.ndarray, list]:
     return flat, table
 
 
-class LSTMScoringServer:
+class LSTMScoringServer(_Server):
     """Persistent per-event LSTM forecaster; ``nkeys`` car keys (ids in [0, nkeys)).
 
     Stacks whose layers are at most 32 wide run from LDS and registers (``kernel`` is
@@ -798,24 +748,3 @@ class LSTMScoringServer:
     def kernel(self) -> str:
         """The resident kernel chosen for this stack: "ref1" | "pipe" | "generic" | "wide"."""
         return str(self._s.kernel)
-
-    @property
-    def launches(self) -> int:
-        return int(self._s.launches)
-
-    def close(self) -> None:
-        if self._s is not None:
-            self._s.stop()
-            self._s = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

@@ -128,6 +128,30 @@ def test_batching_does_not_change_bits(cuda_device, name):
     assert np.array_equal(r.view(np.uint32), r8.view(np.uint32))
 
 
+def test_word_31_is_a_feature_in_every_batching(cuda_device):
+    """Rows of 32 features: request word 31 is the last feature here (the fleet scorer reads a model
+    index there).  Nine rows one per call and the same nine in one call (a backlog: the other waves
+    fetch rows 1..7) give the same bits, within TOL of the float64 reference."""
+    from streamml.ops.serve import DenseScoringServer, dense_layer_table
+    m = _model("one_layer_32", cuda_device)
+    raw = _rows(32)[:9]
+    with DenseScoringServer(m, threshold=THR, slots=256) as srv:
+        one = [srv.infer(raw[i:i + 1]) for i in range(9)]
+        assert srv.passes == 9 and srv.events == 9
+        s9, f9, r9 = srv.infer(raw)
+        print(f"one_layer_32: 9 rows in one call took {srv.passes - 9} passes")
+        assert srv.events == 18
+    s1, f1, r1 = (np.concatenate([o[k] for o in one]) for k in range(3))
+    assert np.array_equal(s1.view(np.uint32), s9.view(np.uint32))
+    assert np.array_equal(f1, f9)
+    assert np.array_equal(r1.view(np.uint32), r9.view(np.uint32))
+    layers, weights = dense_layer_table(m)
+    xn = _normalised(raw)
+    y = forward(layers, weights, xn)
+    ref = score(y, xn)
+    assert np.any(raw[:, 31] != 0) and relerr(r9, y) <= TOL and float(np.max(np.abs(s9 - ref) / ref)) <= TOL
+
+
 def test_reference_shape_matches_the_one_wave_scorer(cuda_device):
     from streamml.models.autoencoder import Autoencoder
     from streamml.ops.serve import DenseScoringServer, ScoringServer

@@ -1,8 +1,15 @@
 """The persistent Dense scorer's limits, weight image and CLI guards, checked without a device:
-``DenseScoringServer.supports`` / ``kernel_for``, ``dense_serve_image`` and ``serve --model dense``."""
+``DenseScoringServer.supports`` / ``kernel_for``, ``dense_serve_image`` and ``serve --model dense``; and
+``supports`` / ``kernel_for`` against the host program over ``sml_dense_fleet_serve.h``
+(``dense_serve_check``, ``dense_serve_in_lds``): the Python mirror and the C++ check must decide
+alike and name the same limit."""
+import os
+import subprocess
+
 import numpy as np
 import pytest
 
+import streamml
 from helpers.dense_serve_ref import forward, forward_image, unpack_image
 from streamml import nn
 from streamml.nn.layers import LSTM, Dense, Dropout
@@ -147,3 +154,66 @@ def test_cli_names_the_cardata_normaliser(tmp_path, monkeypatch):
     m.device = torch.device("cuda", 0)
     with pytest.raises(SystemExit, match="cardata normaliser needs 18"):
         serve_cli._require_dense_servable(m)
+
+
+# ---- supports / kernel_for and the host checker ------------------------------------------------
+PKG = os.path.dirname(os.path.abspath(streamml.__file__))
+
+
+def _tanh_stack(widths, seed=0):
+    return nn.Sequential([Dense(u, "tanh", input_shape=(widths[0],) if i == 0 else None)
+                          for i, u in enumerate(widths[1:])], device="cpu", seed=seed)
+
+
+#          widths, what the refusal names ("" = served)
+SHAPES = [
+    ([18, 64, 16, 64, 18], ""),
+    ([32, 32], ""),                                   # lane 31 is a feature here; the fleet refuses it
+    ([33, 33], "1..32 features"),
+    ([18, 513, 18], "1..512 units"),
+    ([18] + [20] * 8 + [18], "1..8 Dense layers"),    # nine layers
+    ([18, 64, 17], "one unit per feature"),
+    # the two sides of DSV_LDS_IMAGE_BYTES = 94 208: 21 * 448 + 441 * 32 = 23 520 floats = 94 080 bytes,
+    # and 21 * 448 + 445 * 32 = 23 648 floats = 94 592 bytes
+    ([20, 440, 20], ""),
+    ([20, 441, 20], ""),
+]
+KERNELS = {(20, 440, 20): ("lds", 23520), (20, 441, 20): ("stream", 23648)}
+
+
+@pytest.fixture(scope="module")
+def checker(tmp_path_factory):
+    cxx = os.environ.get("CXX", "g++")   # the host compiler the package itself is built with
+    exe = str(tmp_path_factory.mktemp("dense_serve_check") / "dense_fleet_serve_check")
+    subprocess.run([cxx, "-O1", "-std=c++17", "-Wall", "-I", os.path.join(PKG, "csrc", "include"),
+                    os.path.join(PKG, "csrc", "tests", "dense_fleet_serve_check.cpp"), "-o", exe],
+                   check=True, capture_output=True, timeout=120)
+    return exe
+
+
+def test_host_checker_agrees_with_supports_and_kernel_for(checker):
+    text = "".join(",".join(map(str, w)) + "\n" for w, _ in SHAPES)
+    r = subprocess.run([checker, "-s"], input=text, capture_output=True, text=True, timeout=60)
+    assert r.returncode == 0, r.stderr[-2000:]
+    got = [ln.split("\t") for ln in r.stdout.splitlines()]
+    assert len(got) == len(SHAPES)
+    for (widths, names), (why_c, img_floats, where) in zip(SHAPES, got):
+        model = _tanh_stack(widths)
+        ok, why_py = DenseScoringServer.supports(model)
+        # the decision, and the limit both name (Python adds the offending number to its wording)
+        assert ok == (why_c == "") == (names == ""), (widths, why_c, why_py)
+        assert names in why_c and names in why_py, (widths, why_c, why_py)
+        if ok:
+            layers, weights = dense_layer_table(model)
+            assert dense_serve_image(layers, weights)[0].size == int(img_floats)
+            assert DenseScoringServer.kernel_for(model) == where, (widths, img_floats, where)
+        if tuple(widths) in KERNELS:
+            assert (where, int(img_floats)) == KERNELS[tuple(widths)]
+            assert (4 * int(img_floats) <= DenseScoringServer.LDS_IMAGE_BYTES) == (where == "lds")
+
+
+def test_the_fleet_check_refuses_the_32nd_feature(checker):
+    r = subprocess.run([checker], input="32,32 1\n31,31 1\n", capture_output=True, text=True, timeout=60)
+    assert r.returncode == 0, r.stderr[-2000:]
+    why = [ln.split("\t")[0] for ln in r.stdout.splitlines()]
+    assert "1..31 features" in why[0] and why[1] == "", r.stdout
