@@ -95,6 +95,13 @@ def build_c(verbose: bool = False, force: bool = False, checked: bool = False) -
             # interleave VALU with MFMA opt out of SLP packing
             if "sml-build: no-slp" in head:
                 vgpr_form = vgpr_form + ["-fno-slp-vectorize"]
+            # no v_pk_{add,mul,fma}_f32 at all, whichever pass would form them: the device compile runs
+            # without the packed-fp32 target feature (-Xclang also reaches the host pass, which does not
+            # know the feature and ignores it with a warning).  dense_forward.hip: 56 v_pk_fma_f32 without
+            # the switch (the normaliser's fmaf pairs, between MFMAs), none with it, the same 113 / 182 /
+            # 296 VGPRs either way
+            if "sml-build: no-packed-fp32" in head:
+                vgpr_form = vgpr_form + ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
             # SML_HIPCC_EXTRA: extra device-compile flags for A/B builds (e.g. a scheduler strategy)
             extra = os.environ.get("SML_HIPCC_EXTRA", "").split()
             jobs.append([HIPCC, f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-c", src, "-o", obj,

@@ -147,7 +147,8 @@ def _predict(ns, servers, cfg, model, batch_size, result_topic):
         sink = KafkaPredictionSink(batch_size, result_topic, servers, cfg, with_score=ns.with_score)
         cbs.append(sink)
     out = model.predict(data, batch_size=batch_size, callbacks=cbs)
-    print(f"predict {out.shape[0]} events -> {result_topic}", flush=True)
+    eng = getattr(model, "last_predict_engine", None)   # nn.Model (--layers): "fused" | "layers"
+    print(f"predict {out.shape[0]} events -> {result_topic}" + (f" (engine {eng})" if eng else ""), flush=True)
     print("Predict complete", flush=True)
     return out
 

@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "sml_dense_fleet_serve.h"
+#include "sml_dense_fwd_plan.h"
 #include "sml_dense_mb_plan.h"
 
 namespace sml {
@@ -417,6 +418,36 @@ hipError_t dense_mb_fleet_launch(DenseMBArgs args, const DenseMBFleetModel* mode
                                  int64_t stride, hipStream_t stream);
 hipError_t dense_mb_fleet_launch_bf16(const DenseMBArgs& args, const DenseMBFleetModel* models, const int32_t* sched,
                                       int M, int64_t stride, hipStream_t stream);   // args checked by dense_mb_fleet_launch
+
+// ---- fused bulk forward of a Dense stack (dense_forward.hip) ----
+// One launch runs the whole stack over n rows: rows are read once, activations chain from layer to
+// layer in registers on fp32 MFMAs.  xn = x * scale + shift (or x).  Any of: rec [n, out];
+// score [n] = mean((y - xn)^2) with optional flag [n] = score > threshold (needs out == D); sums
+// [dense_fwd_grid()][2] doubles = per-workgroup (sum of per-row mean squared errors, rows whose argmax
+// matches the target's), the target being y [n, out] or xn.  The limits, DenseFwdLayer, the image layout,
+// the LDS plan and dense_fwd_check are in sml_dense_fwd_plan.h (plain C++).
+struct DenseFwdArgs {
+  const float* x;      // [n, D] rows, features contiguous
+  int64_t ldx;
+  int64_t n;
+  const float* image;  // 16-byte aligned
+  int img_floats;
+  const float* scale;  // [D] or null
+  const float* shift;
+  float* rec;          // [n, out] contiguous, or null
+  float* score;        // [n] or null
+  uint8_t* flag;       // [n] or null (needs score)
+  float threshold;
+  double* sums;        // [grid][2] or null
+  const float* y;      // own targets of sums, or null
+  int64_t ldy;
+  int nl, D;
+  int max_blocks;      // 0: one workgroup per CU
+  DenseFwdLayer L[DFW_MAXLAYERS];
+};
+// workgroups dense_fwd_launch starts for n >= 1 rows of a stack that passes dense_fwd_check
+int dense_fwd_grid(const DenseFwdLayer* L, int nl, int D, int64_t n, int max_blocks);
+hipError_t dense_fwd_launch(const DenseFwdArgs& args, hipStream_t stream);
 
 // ---- fused MSE + categorical accuracy (loss.hip) ----
 bool mse_acc_supported(int F);

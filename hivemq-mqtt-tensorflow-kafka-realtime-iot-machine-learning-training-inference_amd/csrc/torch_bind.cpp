@@ -1142,6 +1142,104 @@ std::string dense_mb_check(const std::vector<std::vector<double>>& table, int64_
                              own_targets, (int)std::min<int64_t>(std::max<int64_t>(precision, -1), 2));
 }
 
+// Table rows of the fused bulk forward: (in, units, act, w_off, b_off), offsets in floats of the image.
+static int dense_fwd_table(const std::vector<std::vector<int64_t>>& table, sml::DenseFwdLayer* L) {
+  if (table.size() > (size_t)sml::DFW_MAXLAYERS) return (int)table.size();
+  int nl = 0;
+  for (const auto& t : table) {
+    TORCH_CHECK(t.size() == 5, "layer descriptor: (in, units, act, w_off, b_off)");
+    auto i32 = [](int64_t v) { return (int)std::min<int64_t>(std::max<int64_t>(v, -1), 1 << 30); };
+    L[nl++] = sml::DenseFwdLayer{i32(t[0]), i32(t[1]), i32(t[2]), i32(t[3]), i32(t[4])};
+  }
+  return nl;
+}
+
+// Empty when dense_forward.hip takes the stack (score: against the input row), else the limit it exceeds.
+std::string dense_fwd_check(const std::vector<std::vector<int64_t>>& table, int64_t img_floats, bool score) {
+  sml::DenseFwdLayer L[sml::DFW_MAXLAYERS] = {};
+  const int nl = dense_fwd_table(table, L);
+  return sml::dense_fwd_check(L, nl, nl ? L[0].in : 0, img_floats, score);
+}
+
+// The whole stack over the rows of x in one launch (dense_forward.hip).  rec [n, out], score [n] and
+// flag [n] (uint8) are written where given; sums returns the per-workgroup partials [grid, 2] (float64:
+// sum of per-row mean squared errors, rows whose argmax matches) against y [n, out] or, without y, the
+// normalised row.
+c10::optional<at::Tensor> dense_forward(const at::Tensor& x, const at::Tensor& image,
+                                        const std::vector<std::vector<int64_t>>& table,
+                                        const c10::optional<at::Tensor>& scale, const c10::optional<at::Tensor>& shift,
+                                        const c10::optional<at::Tensor>& rec, const c10::optional<at::Tensor>& score,
+                                        const c10::optional<at::Tensor>& flag, double threshold, bool sums,
+                                        const c10::optional<at::Tensor>& y, int64_t max_blocks) {
+  check_dev(x, "x", at::kFloat);
+  check_dev(image, "image", at::kFloat);
+  TORCH_CHECK(image.dim() == 1 && image.is_contiguous(), "image must be a flat fp32 tensor");
+  for (const c10::optional<at::Tensor>* t : {&scale, &shift, &rec, &score, &flag, &y})
+    TORCH_CHECK(!t->has_value() || (*t)->device() == x.device(), "every tensor must live on x's device");
+  TORCH_CHECK(image.device() == x.device(), "image must live on x's device");
+  sml::DenseFwdArgs a{};
+  const bool scored = score.has_value() || (sums && !y.has_value());
+  const std::string why = dense_fwd_check(table, image.numel(), scored);
+  TORCH_CHECK(why.empty(), "dense_forward: ", why);
+  a.nl = dense_fwd_table(table, a.L);
+  a.D = a.L[0].in;
+  const int64_t O = a.L[a.nl - 1].out, n = x.dim() == 2 ? x.size(0) : 0;
+  TORCH_CHECK(x.dim() == 2 && n >= 1 && x.size(1) == a.D && (a.D == 1 || x.stride(1) == 1) &&
+                  (n == 1 || x.stride(0) >= a.D),
+              "x must be [n >= 1, ", a.D, "] rows with contiguous features");
+  a.x = x.data_ptr<float>();
+  a.ldx = n == 1 ? a.D : x.stride(0);
+  a.n = n;
+  a.image = image.data_ptr<float>();
+  a.img_floats = (int)image.numel();
+  TORCH_CHECK(scale.has_value() == shift.has_value(), "scale and shift come together");
+  if (scale.has_value()) {
+    check_dev(*scale, "scale", at::kFloat);
+    check_dev(*shift, "shift", at::kFloat);
+    TORCH_CHECK(scale->numel() == a.D && shift->numel() == a.D && scale->is_contiguous() && shift->is_contiguous(),
+                "scale / shift must have ", a.D, " entries");
+    a.scale = scale->data_ptr<float>();
+    a.shift = shift->data_ptr<float>();
+  }
+  if (rec.has_value()) {
+    check_dev(*rec, "rec", at::kFloat);
+    TORCH_CHECK(rec->dim() == 2 && rec->size(0) == n && rec->size(1) == O && rec->is_contiguous(), "rec must be a contiguous [n, ",
+                O, "]");
+    a.rec = rec->data_ptr<float>();
+  }
+  if (score.has_value()) {
+    check_dev(*score, "score", at::kFloat);
+    TORCH_CHECK(score->dim() == 1 && score->numel() == n && score->is_contiguous(), "score must be a contiguous [n]");
+    a.score = score->data_ptr<float>();
+  }
+  if (flag.has_value()) {
+    TORCH_CHECK(score.has_value(), "flags need scores");
+    TORCH_CHECK(flag->is_cuda() && (flag->scalar_type() == at::kByte || flag->scalar_type() == at::kBool) && flag->dim() == 1 &&
+                    flag->numel() == n && flag->is_contiguous(), "flag must be a contiguous device uint8 / bool [n]");
+    a.flag = static_cast<uint8_t*>(flag->data_ptr());
+  }
+  a.threshold = (float)threshold;
+  if (y.has_value()) {
+    check_dev(*y, "y", at::kFloat);
+    TORCH_CHECK(sums && !score.has_value(), "own targets are for sums alone");
+    TORCH_CHECK(y->dim() == 2 && y->size(0) == n && y->size(1) == O && (O == 1 || y->stride(1) == 1) &&
+                    (n == 1 || y->stride(0) >= O), "y must be [n, ", O, "] rows with contiguous features");
+    a.y = y->data_ptr<float>();
+    a.ldy = n == 1 ? O : y->stride(0);
+  }
+  TORCH_CHECK(rec.has_value() || score.has_value() || sums, "nothing to compute");
+  TORCH_CHECK(max_blocks >= 0 && max_blocks < (1 << 20), "bad max_blocks");
+  a.max_blocks = (int)max_blocks;
+  c10::hip::HIPGuard guard(x.device().index());
+  c10::optional<at::Tensor> part;
+  if (sums) {
+    part = at::empty({sml::dense_fwd_grid(a.L, a.nl, a.D, n, a.max_blocks), 2}, x.options().dtype(at::kDouble));
+    a.sums = part->data_ptr<double>();
+  }
+  SML_CHECK_HIP(sml::dense_fwd_launch(a, cur_stream(x)));
+  return part;
+}
+
 // How the messages of dense_mb_train and of dense_mb_train_fleet differ: the binding's name, how the row
 // count is written, and what order has to be.
 struct DenseMBWords {
@@ -1918,6 +2016,20 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("flat"), py::arg("m"), py::arg("v"), py::arg("iter"), py::arg("table"), py::arg("x"), py::arg("y"),
         py::arg("order"), py::arg("models"), py::arg("sched"), py::arg("batch"), py::arg("beta1") = 0.9,
         py::arg("beta2") = 0.999, py::arg("eps") = 1e-7, py::arg("precision") = 0);
+  m.def("dense_forward", &dense_forward,
+        "fused bulk forward of a Dense stack (table rows: in, units, act, w_off, b_off of the packed image) in one "
+        "launch: writes rec [n, out] / score [n] / flag [n] where given; sums -> per-workgroup float64 [grid, 2] "
+        "(squared-error sum of the row means, rows with matching argmax) against y or the normalised row",
+        py::arg("x"), py::arg("image"), py::arg("table"), py::arg("scale") = py::none(), py::arg("shift") = py::none(),
+        py::arg("rec") = py::none(), py::arg("score") = py::none(), py::arg("flag") = py::none(),
+        py::arg("threshold") = 0.0, py::arg("sums") = false, py::arg("y") = py::none(), py::arg("max_blocks") = 0);
+  m.def("dense_fwd_check", &dense_fwd_check,
+        "empty if dense_forward takes the table (img_floats < 0: offsets unchecked; score: against the input row), "
+        "else the limit it exceeds",
+        py::arg("table"), py::arg("img_floats") = -1, py::arg("score") = false);
+  m.attr("DFW_MAXLAYERS") = (int)sml::DFW_MAXLAYERS;
+  m.attr("DFW_MAXW") = (int)sml::DFW_MAXW;
+  m.attr("DFW_LDS_BYTES") = (int)sml::DFW_LDS_BYTES;
   m.attr("DMB_MAXLAYERS") = (int)sml::DMB_MAXLAYERS;
   m.attr("DMB_MAXW") = (int)sml::DMB_MAXW;
   m.attr("DMB_MAXBATCH") = (int)sml::DMB_MAXBATCH;

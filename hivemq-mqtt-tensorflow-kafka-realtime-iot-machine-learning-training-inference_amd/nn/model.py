@@ -116,6 +116,9 @@ class Model:
         self._fused_arg: Optional[bool] = None
         self.last_fit_engine: Optional[str] = None
         self.last_fit_precision: Optional[str] = None
+        self.last_predict_engine: Optional[str] = None     # "fused" | "layers" | "autoencoder"
+        self.last_evaluate_engine: Optional[str] = None
+        self.last_score_engine: Optional[str] = None
         self.minibatch_precision: Optional[str] = None
         self._acc = None
         self._pending_opt_state = None
@@ -632,24 +635,85 @@ class Model:
         return hist
 
     # ------------------------------------------------------------------ inference
+    def _bulk_engine(self, what: str, engine: str, x, score: bool = False, need_mse: bool = False) -> bool:
+        """True when the fused bulk forward (``ops.dense_forward``: the whole stack in one launch, fp32)
+        takes this call, False for the layer loop.  ``auto`` takes the kernel when the device is ROCm,
+        the stack is inside its limits and the rows are fp32 (arrays, tensors or a ``Stream``);
+        ``engine="fused"`` raises ``ValueError`` with the reason when it cannot run."""
+        if engine not in ("auto", "fused", "layers"):
+            raise ValueError(f"engine must be 'auto', 'fused' or 'layers', not {engine!r}")
+        if engine == "layers":
+            return False
+        from ..data.stream import Stream
+        from ..ops import dense_forward as dfw
+        why = ""
+        if self.device.type != "cuda":
+            why = f"the model is on {self.device}, not on a ROCm device"
+        elif self._fused is not None:
+            why = "the model runs on the fused autoencoder kernels"
+        elif need_mse and self.loss != "mean_squared_error":
+            why = f"loss {self.loss!r}: the kernel sums mean_squared_error"
+        else:
+            ok, why = dfw.supports(self, score=score)
+            if ok and not isinstance(x, Stream):
+                dt = x.dtype if isinstance(x, torch.Tensor) else np.asarray(x).dtype
+                if dt not in (torch.float32, np.dtype(np.float32)):
+                    why = f"rows of dtype {dt}: the kernel reads fp32"
+        if why and engine == "fused":
+            raise ValueError(f"{what}(engine='fused'): {why}")
+        return not why
+
+    def _bulk_rows(self, xb) -> torch.Tensor:
+        """Rows for the fused kernel: an fp32 device tensor [n, D] with contiguous features."""
+        t = self._prep_x(xb).float()
+        t = t.reshape(len(t), -1)
+        return t if t.stride(1) == 1 or t.shape[1] == 1 else t.contiguous()
+
+    def _bulk_chunks(self, x, chunk: int):
+        from ..data.stream import Stream
+        if isinstance(x, Stream):
+            return (c.x for c in x.batch(chunk))
+        arr = x if isinstance(x, torch.Tensor) else np.asarray(x)
+        return (arr[s:s + chunk] for s in range(0, len(arr), chunk))
+
     @torch.no_grad()
     def predict(self, x, batch_size: int = 32, callbacks: Optional[Sequence[Callback]] = None,
-                verbose: int = 0) -> np.ndarray:
+                verbose: int = 0, engine: str = "auto") -> np.ndarray:
+        """``engine``: "auto" | "fused" | "layers" (see ``_bulk_engine``); ``last_predict_engine`` says
+        which ran.  On the fused path arrays without callbacks run in chunks of
+        ``max(batch_size, 1 << 20)`` rows, each chunk copied into its place in the one host array the call
+        returns as soon as its launch is queued (no join on the device, no second pass on the host); with
+        callbacks or a ``Stream`` every batch is a host array, as in the layer loop.  A model compiled
+        onto the fused autoencoder kernels keeps that path whatever ``engine`` says (``"fused"`` raises)."""
         if not self.compiled:
             self.compile()
-        if self._fused is not None:
+        if self._fused is not None and not self._bulk_engine("predict", engine, x):
+            self.last_predict_engine = "autoencoder"
             return self._fused.predict(x, batch_size=batch_size, callbacks=callbacks)
         from ..data.stream import Stream
         cbs = list(callbacks or [])
         for cb in cbs:
             cb.set_model(self)
         outs = []
-        if isinstance(x, Stream):
-            src = (c.x for c in x.batch(batch_size))
-        else:
-            arr = np.asarray(x) if not isinstance(x, torch.Tensor) else x
-            src = (arr[s:s + batch_size] for s in range(0, len(arr), batch_size))
-        for bi, xb in enumerate(src):
+        if self._bulk_engine("predict", engine, x):
+            from ..ops import dense_forward as dfw
+            self.last_predict_engine = "fused"
+            if not cbs and not isinstance(x, Stream):
+                n, chunk = len(x), max(batch_size, 1 << 20)
+                host = np.empty((n, *self.output_shape), np.float32)
+                for s, xb in zip(range(0, n, chunk), self._bulk_chunks(x, chunk)):
+                    torch.from_numpy(host[s:s + chunk]).copy_(dfw.forward(self, self._bulk_rows(xb))[0])
+                return host
+            for bi, xb in enumerate(self._bulk_chunks(x, batch_size)):
+                out = dfw.forward(self, self._bulk_rows(xb))[0].cpu().numpy()
+                for cb in cbs:
+                    cb.on_predict_batch_end(bi, {"outputs": out})
+                outs.append(out)
+            for cb in cbs:
+                cb.on_predict_end()
+            return np.concatenate(outs) if outs else np.zeros((0, *self.output_shape), np.float32)
+        self.last_predict_engine = "layers"
+        for bi, xb in enumerate(self._bulk_chunks(x, batch_size)):
             out = self._forward(self._prep_x(xb), False).float().cpu().numpy()
             outs.append(out)
             for cb in cbs:
@@ -659,20 +723,89 @@ class Model:
         return np.concatenate(outs) if outs else np.zeros((0, *self.output_shape), np.float32)
 
     @torch.no_grad()
-    def evaluate(self, x, y=None, batch_size: int = 1024, verbose: int = 0) -> Tuple[float, float]:
+    def evaluate(self, x, y=None, batch_size: int = 1024, verbose: int = 0, engine: str = "auto") -> Tuple[float, float]:
+        """(loss, accuracy).  On the fused path (``engine``, ``last_evaluate_engine``: as ``predict``; the
+        loss must be mean_squared_error) the whole array is one launch and one host read.  A model compiled
+        onto the fused autoencoder kernels keeps that path whatever ``engine`` says (``"fused"`` raises)."""
         if not self.compiled:
             self.compile()
-        if self._fused is not None:
+        if self._fused is not None and not self._bulk_engine("evaluate", engine, x):
+            self.last_evaluate_engine = "autoencoder"
             return self._fused.evaluate(x, batch_size=max(batch_size, 65536))
-        tot = np.zeros(3)
         xs = np.asarray(x) if not isinstance(x, torch.Tensor) else x
         ys = xs if y is None else (np.asarray(y) if not isinstance(y, torch.Tensor) else y)
+        if self._bulk_engine("evaluate", engine, xs, score=y is None, need_mse=True):
+            from ..ops import dense_forward as dfw
+            xd = self._bulk_rows(xs)
+            yd = None if y is None else self._bulk_rows(ys)
+            if yd is not None and tuple(yd.shape) != (len(xd), int(self.output_shape[-1])):
+                if engine == "fused":
+                    raise ValueError(f"evaluate(engine='fused'): y of shape {tuple(yd.shape)} is not "
+                                     f"[{len(xd)}, {int(self.output_shape[-1])}] rows")
+            else:
+                self.last_evaluate_engine = "fused"
+                loss, corr = dfw.evaluate_sums(self, xd, yd)
+                n = max(len(xd), 1)
+                return loss / n, corr / n
+        self.last_evaluate_engine = "layers"
+        tot = np.zeros(3)
         for s in range(0, len(xs), batch_size):
             xb, yb = self._prep_x(xs[s:s + batch_size]), self._prep_y(ys[s:s + batch_size])
             loss, corr = self._loss_and_metric(xb, yb, False)
             tot += [float(loss) * len(xb), float(corr), len(xb)]
         n = max(tot[2], 1)
         return float(tot[0] / n), float(tot[1] / n)
+
+    @torch.no_grad()
+    def _score_pass(self, x, normalizer, batch_size: int, engine: str, rec: bool, threshold: Optional[float]):
+        """(reconstructions | None, scores, flags | None) as host arrays: one fused launch per
+        ``batch_size`` rows, or the layer loop."""
+        if not self.compiled:
+            self.compile()
+        D = int(self._input_shape()[0])
+        if len(self._input_shape()) != 1 or tuple(self.output_shape) != (D,):
+            raise ValueError(f"scores need a stack with one unit per feature (input {tuple(self._input_shape())}, "
+                             f"output {tuple(self.output_shape)})")
+        fused = self._bulk_engine("score", engine, x, score=True)
+        self.last_score_engine = "fused" if fused else "layers"
+        sc = sh = None
+        if fused:
+            from ..ops import dense_forward as dfw
+        else:
+            from ..ops.serve import _resolve_normalizer
+            sc, sh = _resolve_normalizer(normalizer, D, self, "the model has")
+            if sc is not None:
+                sc, sh = torch.from_numpy(sc).to(self.device), torch.from_numpy(sh).to(self.device)
+        parts = []
+        for xb in self._bulk_chunks(x, max(int(batch_size), 1)):
+            xd = self._bulk_rows(xb)
+            if fused:
+                parts.append(dfw.forward(self, xd, rec=rec, score=True, threshold=threshold, normalizer=normalizer))
+            else:
+                xn = xd if sc is None else xd * sc + sh
+                r = self._forward(xn, False).float()
+                s = ((r - xn) ** 2).mean(dim=1)
+                parts.append((r if rec else None, s, None if threshold is None else s > threshold))
+        empty = (np.zeros((0, D), np.float32), np.zeros(0, np.float32), np.zeros(0, bool))
+        return tuple(None if not want else e if not parts else torch.cat([p[k] for p in parts]).cpu().numpy()
+                     for k, (want, e) in enumerate(zip((rec, True, threshold is not None), empty)))
+
+    def reconstruct_and_score(self, x, normalizer=None, batch_size: int = 1 << 20,
+                              engine: str = "auto") -> Tuple[np.ndarray, np.ndarray]:
+        """(reconstructions [n, D], scores [n]) of an autoencoding stack (one unit per feature) from one
+        device pass, with ``models.Autoencoder``'s semantics: ``xn = x * scale + shift``,
+        ``score = mean((y - xn)^2)``.  ``normalizer``: None, ``"cardata"`` or a ``(scale, shift)`` pair.
+        ``engine`` / ``last_score_engine``: as ``predict``."""
+        return self._score_pass(x, normalizer, batch_size, engine, True, None)[:2]
+
+    def score(self, x, normalizer=None, batch_size: int = 1 << 20, engine: str = "auto") -> np.ndarray:
+        """Per-row reconstruction error ``mean((y - xn)^2)``: see ``reconstruct_and_score``."""
+        return self._score_pass(x, normalizer, batch_size, engine, False, None)[1]
+
+    def detect(self, x, threshold: float = 5.0, normalizer=None, batch_size: int = 1 << 20,
+               engine: str = "auto") -> np.ndarray:
+        """Anomaly flags ``score > threshold`` (the fused kernel writes them with the scores)."""
+        return self._score_pass(x, normalizer, batch_size, engine, False, float(threshold))[2]
 
     # ------------------------------------------------------------------ weights / summary
     def get_weights(self) -> List[np.ndarray]:
