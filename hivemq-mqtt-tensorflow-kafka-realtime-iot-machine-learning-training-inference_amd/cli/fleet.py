@@ -14,7 +14,7 @@ on rows normalised once on the host; every ``.h5`` is one ``serve --model dense`
 ``serve --model dense-fleet <dir>`` scores the live stream with, every car by its own model.
 
   fleet <csv|synthetic> [--models N] [--epochs E] [--batch 32] [--lr 1e-3] [--out DIR]
-        [--layers 64,16,64 [--precision fp32|bf16]]
+        [--layers 64,16,64 [--precision fp32|bf16] [--threshold-quantile Q]]
 """
 from __future__ import annotations
 
@@ -43,9 +43,15 @@ def parse_args(argv: Sequence[str]):
                         "last): trains a fleet of such stacks on the persistent Dense trainer")
     p.add_argument("--precision", default=None, choices=["fp32", "bf16"],
                    help="with --layers: the trainer's contractions, fp32 (default) or bf16 MFMAs")
+    # absent from the namespace unless given: what fleet parses without it is unchanged
+    p.add_argument("--threshold-quantile", type=float, default=argparse.SUPPRESS, metavar="Q",
+                   help="with --layers: after training, write each member's anomaly threshold into index.json, "
+                        "the Q order statistic of its own training rows' scores (DenseFleet.calibrate_thresholds)")
     ns = p.parse_args(list(argv))
     if ns.precision is not None and ns.layers is None:
         p.error("--precision goes with --layers")
+    if hasattr(ns, "threshold_quantile") and ns.layers is None:
+        p.error("--threshold-quantile goes with --layers")
     return ns
 
 
@@ -80,11 +86,15 @@ def training_rows(ns):
 INDEX_META = ("layers", "engine", "precision")   # keys of index.json beside the models' names (--layers)
 
 
-def build_index(names, members, losses, layers=None, precision=None) -> dict:
+def build_index(names, members, losses, layers=None, precision=None, thresholds=None) -> dict:
     """``index.json``: name -> {file, keys, loss}; for a ``--layers`` fleet also the stack's hidden
-    widths, the engine that trained it and its precision."""
+    widths, the engine that trained it and its precision.  ``thresholds`` (one per member) adds each
+    member's ``threshold``."""
     index = {name: {"file": name + ".h5", "keys": [str(k) for k in members[i]], "loss": losses[i]}
              for i, name in enumerate(names)}
+    if thresholds is not None:
+        for i, name in enumerate(names):
+            index[name]["threshold"] = float(thresholds[i])
     if layers is not None:
         index.update(layers=[int(w) for w in layers], engine="persistent", precision=precision or "fp32")
     return index
@@ -145,7 +155,10 @@ def _main_layers(ns) -> int:
     names = [model_name(members, i, used) for i in range(M)]
     for i, name in enumerate(names):
         fleet.model(i, device="cpu").save(os.path.join(ns.out, name + ".h5"))
-    index = build_index(names, members, [ms[i]["loss"] if ms else None for i in range(M)], hidden, precision)
+    thresholds = None
+    if hasattr(ns, "threshold_quantile"):   # on the (already normalised) training rows
+        thresholds = fleet.calibrate_thresholds(ns.threshold_quantile)
+    index = build_index(names, members, [ms[i]["loss"] if ms else None for i in range(M)], hidden, precision, thresholds)
     with open(os.path.join(ns.out, "index.json"), "w") as f:
         json.dump(index, f, indent=1)
     print(f"wrote {M} models to {ns.out}", flush=True)

@@ -108,6 +108,9 @@ def _flags(p) -> None:
     p.add_argument("--fallback-model", default=None, metavar="NAME",
                    help="--model dense-fleet: score cars that index.json does not name with this member "
                         "(default: drop them, counted as keys_dropped)")
+    p.add_argument("--calibrated-thresholds", action="store_true",
+                   help="--model dense-fleet: flag every car against its own member's threshold from index.json "
+                        "(fleet --threshold-quantile wrote them) instead of --threshold")
     p.add_argument("--max-keys", type=int, default=200_000, help="--model lstm: car keys held on the device")
     p.add_argument("--lanes", type=int, default=1,
                    help="--model lstm: resident workgroups of the forecaster; car key k is served by lane "
@@ -168,16 +171,22 @@ class _FleetDir:
 
     name = "dense-fleet"
 
-    def __init__(self, path: str, device, fallback=None):
+    def __init__(self, path: str, device, fallback=None, calibrated: bool = False):
         import torch
 
-        from ..ops.serve import DenseFleetScoringServer
+        from ..ops.serve import DenseFleetScoringServer, read_fleet_thresholds
         if not os.path.isdir(path):
             raise SystemExit(f"--model dense-fleet: {path} is not a directory (expected the output of fleet --layers)")
         try:
             self.models, self.names, self.key_to_model = DenseFleetScoringServer.load_dir(path)
         except ValueError as e:
             raise SystemExit(f"--model dense-fleet: {e}")
+        self.thresholds = None
+        if calibrated:
+            try:
+                self.thresholds = read_fleet_thresholds(path)
+            except ValueError as e:
+                raise SystemExit(f"--calibrated-thresholds: {e}")
         features = int(self.models[0]._input_shape()[0])
         if features != 18:
             raise SystemExit(f"--model dense-fleet: the cardata normaliser needs 18 input features, the models "
@@ -193,8 +202,8 @@ class _FleetDir:
 
     def server(self, threshold: float, slots: int = 4096):
         from ..ops.serve import DenseFleetScoringServer
-        return DenseFleetScoringServer(self.models, thresholds=threshold, normalizer="cardata", slots=slots,
-                                       device=self.device)
+        thr = threshold if self.thresholds is None else self.thresholds
+        return DenseFleetScoringServer(self.models, thresholds=thr, normalizer="cardata", slots=slots, device=self.device)
 
     def indices(self, keys):
         """(model index per record, -1 for a car no member owns and no fallback takes)."""
@@ -284,6 +293,8 @@ def main(argv: Sequence[str]) -> int:
 
     if ns.fallback_model is not None and ns.model != "dense-fleet":
         raise SystemExit("--fallback-model goes with --model dense-fleet")
+    if ns.calibrated_thresholds and ns.model != "dense-fleet":
+        raise SystemExit("--calibrated-thresholds goes with --model dense-fleet")
     path = common.model_path(ns.workdir, ns.model_file)
     if ns.model == "dense-fleet":
         if not os.path.isdir(path) and os.path.isdir(ns.model_file):
@@ -295,7 +306,7 @@ def main(argv: Sequence[str]) -> int:
         else:
             autoencoder_store(ns.project, ns.store).download("/" + ns.model_file, path)
     if ns.model == "dense-fleet":
-        model = _FleetDir(path, device, ns.fallback_model)
+        model = _FleetDir(path, device, ns.fallback_model, ns.calibrated_thresholds)
     elif ns.model == "lstm":
         from ..models.lstm import LSTMPredictor
         model = LSTMPredictor.load(path, device=device)

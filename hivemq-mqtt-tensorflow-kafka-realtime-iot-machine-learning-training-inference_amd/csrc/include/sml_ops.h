@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "sml_dense_fleet_serve.h"
+#include "sml_dense_fleet_fwd.h"
 #include "sml_dense_fwd_plan.h"
 #include "sml_dense_mb_plan.h"
 
@@ -448,6 +449,43 @@ struct DenseFwdArgs {
 // workgroups dense_fwd_launch starts for n >= 1 rows of a stack that passes dense_fwd_check
 int dense_fwd_grid(const DenseFwdLayer* L, int nl, int D, int64_t n, int max_blocks);
 hipError_t dense_fwd_launch(const DenseFwdArgs& args, hipStream_t stream);
+
+// ---- the same forward for a fleet of stacks of one shape (dense_forward_fleet.hip) ----
+// Model m runs over rows table[m] = {first row, rows} of x with image images + m * stride; a row's
+// bits are those dense_fwd_launch gives with that image.  Any of rec [n, out], score [n] with flag [n]
+// = score > thr[m], and sums: slot m + b of slot_sums [M + grid][2] / slot_model [M + grid] takes the
+// (loss, correct rows) doubles of workgroup b's rows of model m and the index m (the caller fills
+// slot_model with -1 and folds the slots in order).  Rows no slice covers are not written.  The pair
+// space, the plan and dense_fleet_fwd_check are in sml_dense_fleet_fwd.h (plain C++).
+struct DenseFleetFwdArgs {
+  const float* x;             // [n, D] rows, features contiguous
+  int64_t ldx;
+  int64_t n;
+  const float* images;        // [M][stride], 16-byte aligned
+  int64_t stride;             // floats, a multiple of DFF_IMG_ALIGN
+  int img_floats;
+  int M;
+  const int64_t* table;       // device [M][2]; the host's copy is checked by the caller
+  const int64_t* pair_base;   // device [M + 1]
+  int64_t pairs;              // pair_base[M], known to the host
+  const float* thr;           // device [M], or null (no flags)
+  const float* scale;         // [D] or null
+  const float* shift;
+  float* rec;
+  float* score;
+  uint8_t* flag;              // needs score and thr
+  double* slot_sums;          // [M + grid][2] or null
+  int32_t* slot_model;        // [M + grid]
+  const float* y;             // own targets of sums, or null
+  int64_t ldy;
+  int nl, D;
+  int max_blocks;             // 0: one workgroup per CU
+  int plain_copy;             // 1: images reach LDS through registers, not by global-to-LDS loads
+  DenseFwdLayer L[DFW_MAXLAYERS];
+};
+// workgroups dense_fleet_fwd_launch starts for `pairs` >= 1 tile pairs
+int dense_fleet_fwd_grid(const DenseFwdLayer* L, int nl, int D, int64_t pairs, int max_blocks);
+hipError_t dense_fleet_fwd_launch(const DenseFleetFwdArgs& args, hipStream_t stream);
 
 // ---- fused MSE + categorical accuracy (loss.hip) ----
 bool mse_acc_supported(int F);

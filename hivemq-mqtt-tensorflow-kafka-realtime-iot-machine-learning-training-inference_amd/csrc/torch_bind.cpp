@@ -1240,6 +1240,154 @@ c10::optional<at::Tensor> dense_forward(const at::Tensor& x, const at::Tensor& i
   return part;
 }
 
+// ---- the fleet variant (dense_forward_fleet.hip, sml_dense_fleet_fwd.h) ----
+static const int64_t* fleet_rows_table(const c10::optional<at::Tensor>& t, int64_t M) {
+  if (!t.has_value()) return nullptr;
+  TORCH_CHECK(!t->is_cuda() && t->scalar_type() == at::kLong && t->dim() == 2 && t->size(0) == M && t->size(1) == 2 &&
+                  t->is_contiguous(), "rows_table must be a contiguous host int64 [", M, ", 2]");
+  return t->data_ptr<int64_t>();
+}
+
+std::string dense_fleet_fwd_check(const std::vector<std::vector<int64_t>>& table, bool score, int64_t n_models,
+                                  const c10::optional<at::Tensor>& rows_table, int64_t n_rows, int64_t stride) {
+  sml::DenseFwdLayer L[sml::DFW_MAXLAYERS] = {};
+  const int nl = dense_fwd_table(table, L);
+  if (nl >= 1 && nl <= sml::DFW_MAXLAYERS) sml::dense_fwd_image_offsets(L, nl);
+  const bool sized = n_models >= 1 && n_models < sml::DFF_MAXMODELS;
+  return sml::dense_fleet_fwd_check(L, nl, nl ? L[0].in : 0, -1, score, n_models,
+                                    sized ? fleet_rows_table(rows_table, n_models) : nullptr, n_rows, stride);
+}
+
+std::vector<int64_t> dense_fleet_fwd_plan(const std::vector<std::vector<int64_t>>& table) {
+  sml::DenseFwdLayer L[sml::DFW_MAXLAYERS] = {};
+  const int nl = dense_fwd_table(table, L);
+  const std::string why = sml::dense_fwd_check(L, nl, nl ? L[0].in : 0, -1, false);
+  TORCH_CHECK(why.empty(), "dense_fleet_fwd_plan: ", why);
+  const sml::DenseFleetFwdPlan F = sml::dense_fleet_fwd_plan(L, nl, L[0].in);
+  return {F.one.mb, F.nbuf, F.img2_off, F.waves, F.one.stride, F.one.lds_bytes};
+}
+
+std::pair<std::vector<int64_t>, std::vector<std::vector<int64_t>>> dense_fleet_fwd_walk(const at::Tensor& rows_table,
+                                                                                        int64_t grid) {
+  const int64_t M = rows_table.dim() == 2 ? rows_table.size(0) : 0;
+  TORCH_CHECK(M >= 1 && grid >= 1, "a fleet and a grid of at least one");
+  const int64_t* t = fleet_rows_table(rows_table, M);
+  std::vector<int64_t> pb(M + 1);
+  sml::dense_fleet_fwd_pair_base(t, M, pb.data());
+  std::vector<std::vector<int64_t>> segs;
+  for (int64_t b = 0; b < grid; ++b)
+    sml::dense_fleet_fwd_walk(pb.data(), M, grid, b, [&](int64_t m, int64_t slot, int64_t p0, int64_t p1) {
+      segs.push_back({b, m, slot, p0, p1});
+    });
+  return {pb, segs};
+}
+
+// rows_table is the host's [M, 2] (checked here), rows_table_dev / pair_base_dev its device copies
+// (pair_base [M + 1] as dense_fleet_fwd_walk returns it): the caller keeps them between launches.
+c10::optional<std::tuple<at::Tensor, at::Tensor>> dense_forward_fleet(
+    const at::Tensor& x, const at::Tensor& images, const std::vector<std::vector<int64_t>>& table,
+    const at::Tensor& rows_table, const at::Tensor& rows_table_dev, const at::Tensor& pair_base_dev,
+    const c10::optional<at::Tensor>& scale, const c10::optional<at::Tensor>& shift, const c10::optional<at::Tensor>& rec,
+    const c10::optional<at::Tensor>& score, const c10::optional<at::Tensor>& flag, const c10::optional<at::Tensor>& thr,
+    bool sums, const c10::optional<at::Tensor>& y, int64_t max_blocks, bool plain_copy) {
+  check_dev(x, "x", at::kFloat);
+  check_dev(images, "images", at::kFloat);
+  TORCH_CHECK(images.dim() == 2 && images.is_contiguous() && images.device() == x.device(),
+              "images must be a contiguous fp32 [M, stride] on x's device");
+  for (const c10::optional<at::Tensor>* t : {&scale, &shift, &rec, &score, &flag, &thr, &y})
+    TORCH_CHECK(!t->has_value() || (*t)->device() == x.device(), "every tensor must live on x's device");
+  const int64_t M = images.size(0);
+  sml::DenseFleetFwdArgs a{};
+  a.nl = dense_fwd_table(table, a.L);
+  const bool scored = score.has_value() || (sums && !y.has_value());
+  TORCH_CHECK(x.dim() == 2, "x must be [n, D]");
+  const int64_t n = x.size(0);
+  const bool sized = M >= 1 && M < sml::DFF_MAXMODELS;
+  const int64_t* host = sized ? fleet_rows_table(rows_table, M) : nullptr;
+  const bool laid = a.nl >= 1 && a.nl <= sml::DFW_MAXLAYERS;
+  const int64_t want_floats = laid ? a.L[a.nl - 1].b_off + sml::dfw_pad16(a.L[a.nl - 1].out) : 0;
+  const std::string why = sml::dense_fleet_fwd_check(a.L, a.nl, a.nl ? a.L[0].in : 0, want_floats, scored, M, host, n,
+                                                     images.size(1));
+  TORCH_CHECK(why.empty(), "dense_forward_fleet: ", why);
+  a.D = a.L[0].in;
+  const int64_t O = a.L[a.nl - 1].out;
+  TORCH_CHECK(n >= 1 && x.size(1) == a.D && (a.D == 1 || x.stride(1) == 1) && (n == 1 || x.stride(0) >= a.D),
+              "x must be [n >= 1, ", a.D, "] rows with contiguous features");
+  for (const at::Tensor* t : {&rows_table_dev, &pair_base_dev})
+    TORCH_CHECK(t->is_cuda() && t->device() == x.device() && t->scalar_type() == at::kLong && t->is_contiguous(),
+                "rows_table_dev / pair_base_dev must be contiguous int64 on x's device");
+  TORCH_CHECK(rows_table_dev.numel() == 2 * M && pair_base_dev.numel() == M + 1, "rows_table_dev [M, 2], pair_base_dev [M + 1]");
+  std::vector<int64_t> pb(M + 1);
+  sml::dense_fleet_fwd_pair_base(host, M, pb.data());
+  a.x = x.data_ptr<float>();
+  a.ldx = n == 1 ? a.D : x.stride(0);
+  a.n = n;
+  a.images = images.data_ptr<float>();
+  a.stride = images.size(1);
+  a.img_floats = (int)want_floats;
+  a.M = (int)M;
+  a.table = rows_table_dev.data_ptr<int64_t>();
+  a.pair_base = pair_base_dev.data_ptr<int64_t>();
+  a.pairs = pb[M];
+  TORCH_CHECK(scale.has_value() == shift.has_value(), "scale and shift come together");
+  if (scale.has_value()) {
+    check_dev(*scale, "scale", at::kFloat);
+    check_dev(*shift, "shift", at::kFloat);
+    TORCH_CHECK(scale->numel() == a.D && shift->numel() == a.D && scale->is_contiguous() && shift->is_contiguous(),
+                "scale / shift must have ", a.D, " entries");
+    a.scale = scale->data_ptr<float>();
+    a.shift = shift->data_ptr<float>();
+  }
+  if (rec.has_value()) {
+    check_dev(*rec, "rec", at::kFloat);
+    TORCH_CHECK(rec->dim() == 2 && rec->size(0) == n && rec->size(1) == O && rec->is_contiguous(),
+                "rec must be a contiguous [n, ", O, "]");
+    a.rec = rec->data_ptr<float>();
+  }
+  if (score.has_value()) {
+    check_dev(*score, "score", at::kFloat);
+    TORCH_CHECK(score->dim() == 1 && score->numel() == n && score->is_contiguous(), "score must be a contiguous [n]");
+    a.score = score->data_ptr<float>();
+  }
+  if (flag.has_value()) {
+    TORCH_CHECK(score.has_value() && thr.has_value(), "flags need scores and thresholds");
+    TORCH_CHECK(flag->is_cuda() && (flag->scalar_type() == at::kByte || flag->scalar_type() == at::kBool) && flag->dim() == 1 &&
+                    flag->numel() == n && flag->is_contiguous(), "flag must be a contiguous device uint8 / bool [n]");
+    check_dev(*thr, "thr", at::kFloat);
+    TORCH_CHECK(thr->numel() == M && thr->is_contiguous(), "thr must be a contiguous [M]");
+    a.flag = static_cast<uint8_t*>(flag->data_ptr());
+    a.thr = thr->data_ptr<float>();
+  }
+  if (y.has_value()) {
+    check_dev(*y, "y", at::kFloat);
+    TORCH_CHECK(sums && !score.has_value(), "own targets are for sums alone");
+    TORCH_CHECK(y->dim() == 2 && y->size(0) == n && y->size(1) == O && (O == 1 || y->stride(1) == 1) &&
+                    (n == 1 || y->stride(0) >= O), "y must be [n, ", O, "] rows with contiguous features");
+    a.y = y->data_ptr<float>();
+    a.ldy = n == 1 ? O : y->stride(0);
+  }
+  TORCH_CHECK(rec.has_value() || score.has_value() || sums, "nothing to compute");
+  TORCH_CHECK(max_blocks >= 0 && max_blocks < (1 << 20), "bad max_blocks");
+  a.max_blocks = (int)max_blocks;
+  a.plain_copy = plain_copy ? 1 : 0;
+  c10::optional<std::tuple<at::Tensor, at::Tensor>> out;
+  if (a.pairs < 1) {   // no model has rows: nothing to launch
+    if (sums) out = std::make_tuple(at::zeros({M, 2}, x.options().dtype(at::kDouble)), at::full({M}, -1, x.options().dtype(at::kInt)));
+    return out;
+  }
+  c10::hip::HIPGuard guard(x.device().index());
+  if (sums) {
+    const int64_t slots = M + sml::dense_fleet_fwd_grid(a.L, a.nl, a.D, a.pairs, a.max_blocks);
+    at::Tensor part = at::zeros({slots, 2}, x.options().dtype(at::kDouble));
+    at::Tensor model = at::full({slots}, -1, x.options().dtype(at::kInt));
+    a.slot_sums = part.data_ptr<double>();
+    a.slot_model = model.data_ptr<int32_t>();
+    out = std::make_tuple(part, model);
+  }
+  SML_CHECK_HIP(sml::dense_fleet_fwd_launch(a, cur_stream(x)));
+  return out;
+}
+
 // How the messages of dense_mb_train and of dense_mb_train_fleet differ: the binding's name, how the row
 // count is written, and what order has to be.
 struct DenseMBWords {
@@ -2027,6 +2175,26 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "empty if dense_forward takes the table (img_floats < 0: offsets unchecked; score: against the input row), "
         "else the limit it exceeds",
         py::arg("table"), py::arg("img_floats") = -1, py::arg("score") = false);
+  m.def("dense_forward_fleet", &dense_forward_fleet,
+        "fused bulk forward of a fleet of Dense stacks in one launch: model m (image images[m]) over rows "
+        "table[m] = {first row, rows} of x; writes rec / score / flag (score > thr[m]) where given; sums -> "
+        "(slot sums [M + grid, 2] float64, slot model [M + grid] int32, -1 for an unused slot)",
+        py::arg("x"), py::arg("images"), py::arg("table"), py::arg("rows_table"), py::arg("rows_table_dev"),
+        py::arg("pair_base_dev"), py::arg("scale") = py::none(), py::arg("shift") = py::none(),
+        py::arg("rec") = py::none(), py::arg("score") = py::none(), py::arg("flag") = py::none(),
+        py::arg("thr") = py::none(), py::arg("sums") = false, py::arg("y") = py::none(), py::arg("max_blocks") = 0,
+        py::arg("plain_copy") = false);
+  m.def("dense_fleet_fwd_check", &dense_fleet_fwd_check,
+        "empty if dense_forward_fleet takes M such stacks (rows_table [M, 2] int64 on the host or None, stride < 0: "
+        "unchecked), else the limit it exceeds",
+        py::arg("table"), py::arg("score"), py::arg("n_models"), py::arg("rows_table") = py::none(),
+        py::arg("n_rows") = 0, py::arg("stride") = -1);
+  m.def("dense_fleet_fwd_plan", &dense_fleet_fwd_plan, "(mb, nbuf, img2_off, waves, stride, lds_bytes) of the table",
+        py::arg("table"));
+  m.def("dense_fleet_fwd_walk", &dense_fleet_fwd_walk,
+        "(pair_base [M + 1], segments [(workgroup, model, slot, first local pair, end)]) of a launch of `grid` workgroups",
+        py::arg("rows_table"), py::arg("grid"));
+  m.attr("DFF_IMG_ALIGN") = (int)sml::DFF_IMG_ALIGN;
   m.attr("DFW_MAXLAYERS") = (int)sml::DFW_MAXLAYERS;
   m.attr("DFW_MAXW") = (int)sml::DFW_MAXW;
   m.attr("DFW_LDS_BYTES") = (int)sml::DFW_LDS_BYTES;

@@ -120,6 +120,7 @@ class DenseFleet:
         self._pending: list = []          # (out [M, S, 2], steps [M], rows of each model's last step [M])
         self._launches = 0
         self.last_out: Optional[torch.Tensor] = None    # [M, S, 2] of the latest launch: per step (loss, correct rows)
+        self.last_forward_launches = 0                  # launches of the latest score / detect / evaluate / ...
 
     @classmethod
     def from_seeds(cls, build, seeds: Sequence[int], device, **kw) -> "DenseFleet":
@@ -283,6 +284,64 @@ class DenseFleet:
         d = np.maximum(rows, 1.0)
         return [{"loss": float(loss[i] / d[i]), "accuracy": float(corr[i] / d[i]), "rows": float(rows[i])}
                 for i in range(M)]
+
+    # -- bulk inference: every member over its own rows, one fused launch (ops/dense_fleet_forward.py) --
+    # fp32 whatever the training precision, as the scorers
+    def _rows_arg(self, rows, table):
+        if rows is None:
+            self._need_rows()
+            rows = self.x
+        if table is None:
+            self._need_rows()
+            table = self._rows_table
+        return rows, np.asarray(table)
+
+    def reconstruct_and_score(self, rows=None, table=None, normalizer=None, thresholds=None, max_blocks: int = 0):
+        """(reconstructions [N, out], scores [N], flags [N] bool or None) on the device: member m over
+        ``rows[table[m, 0] : table[m, 0] + table[m, 1]]`` (default: the attached rows and table).  Rows no
+        slice covers hold NaN / False."""
+        from . import dense_fleet_forward as dff
+        rows, table = self._rows_arg(rows, table)
+        return dff.forward(self, rows, table, rec=True, score=True, thresholds=thresholds, normalizer=normalizer,
+                           max_blocks=max_blocks)
+
+    def score(self, rows=None, table=None, normalizer=None, max_blocks: int = 0) -> torch.Tensor:
+        """Device scores [N]: ``mean((y - xn)^2)`` of every row under its own member."""
+        from . import dense_fleet_forward as dff
+        rows, table = self._rows_arg(rows, table)
+        return dff.forward(self, rows, table, rec=False, score=True, normalizer=normalizer, max_blocks=max_blocks)[1]
+
+    def detect(self, rows=None, table=None, thresholds=5.0, normalizer=None, max_blocks: int = 0) -> torch.Tensor:
+        """Device flags [N] bool: ``score > thresholds[m]`` (one number or one per member)."""
+        from . import dense_fleet_forward as dff
+        rows, table = self._rows_arg(rows, table)
+        return dff.forward(self, rows, table, rec=False, score=True, thresholds=thresholds, normalizer=normalizer,
+                           max_blocks=max_blocks)[2]
+
+    def evaluate(self, rows=None, table=None, y=None, normalizer=None, max_blocks: int = 0) -> List[dict]:
+        """Per member ``{loss, accuracy, rows}`` over its own rows: the MSE without penalties against ``y``
+        (default: the attached targets, else the row itself) and the share of rows whose argmax matches."""
+        from . import dense_fleet_forward as dff
+        if rows is None and y is None:
+            y = self.y
+        rows, table = self._rows_arg(rows, table)
+        loss, correct = dff.evaluate_sums(self, rows, table, y=y, normalizer=normalizer, max_blocks=max_blocks)
+        n = table[:, 1].astype(np.float64)
+        d = np.maximum(n, 1.0)
+        return [{"loss": float(loss[i] / d[i]), "accuracy": float(correct[i] / d[i]), "rows": float(n[i])}
+                for i in range(self.n_models)]
+
+    def calibrate_thresholds(self, q: float, rows=None, table=None, normalizer=None) -> np.ndarray:
+        """``[M]`` float32 for ``server(thresholds=...)``: member m's value is
+        ``np.quantile(scores_m, q, method="higher")`` of its own rows' scores, found on the device."""
+        from . import dense_fleet_forward as dff
+        if not 0.0 <= float(q) <= 1.0:
+            raise ValueError(f"q must be in [0, 1], not {q}")
+        rows, table = self._rows_arg(rows, table)
+        if table.shape == (self.n_models, 2) and (table[:, 1] < 1).any():
+            raise ValueError(f"model {int(np.flatnonzero(table[:, 1] < 1)[0])} has no rows to calibrate on")
+        scores = dff.forward(self, rows, table, rec=False, score=True, normalizer=normalizer)[1]
+        return dff.segmented_quantiles(scores, np.ascontiguousarray(table, np.int64), float(q))
 
     # -- state -------------------------------------------------------------------------
     def _check_index(self, i: int) -> int:

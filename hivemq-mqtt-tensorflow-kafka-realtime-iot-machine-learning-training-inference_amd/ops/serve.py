@@ -494,8 +494,13 @@ class DenseFleetScoringServer(_DenseServer):
     def from_dir(cls, path, **kw) -> "DenseFleetScoringServer":
         """Serve the directory ``fleet --layers`` wrote: ``index.json`` names the members' files and
         the car keys each one owns.  ``names[i]`` is member i's name and ``key_to_model`` maps a car
-        key to its member's index."""
+        key to its member's index.  ``thresholds="index"`` takes every member's ``threshold`` from the
+        index (``fleet --threshold-quantile`` writes them)."""
         models, names, key_to_model = cls.load_dir(path)
+        if isinstance(kw.get("thresholds"), str):
+            if kw["thresholds"] != "index":
+                raise ValueError(f"thresholds must be numbers or 'index', not {kw['thresholds']!r}")
+            kw["thresholds"] = read_fleet_thresholds(path)
         if kw.get("device", None) is None:
             kw["device"] = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else "cpu"
         self = cls(models, **kw)
@@ -599,6 +604,21 @@ def read_fleet_index(path) -> Tuple[list, list, dict]:
         for k in index[n].get("keys", []):
             key_to_model[str(k)] = i
     return names, files, key_to_model
+
+
+def read_fleet_thresholds(path) -> np.ndarray:
+    """``[M]`` float32: the ``threshold`` of every member of a ``fleet --layers`` directory, in
+    ``read_fleet_index``'s order.  A member without one is a ``ValueError`` that names it."""
+    import json
+    import os
+    names = read_fleet_index(path)[0]
+    with open(os.path.join(str(path), "index.json")) as f:
+        index = json.load(f)
+    missing = [n for n in names if "threshold" not in index[n]]
+    if missing:
+        raise ValueError(f"{path}: index.json has no 'threshold' for {missing[0]!r} ({len(missing)} of {len(names)} "
+                         f"members): train with fleet --threshold-quantile")
+    return np.array([index[n]["threshold"] for n in names], np.float32)
 
 
 def lstm_layer_table(model) -> Tuple[np.ndarray, list]:
