@@ -50,6 +50,10 @@ def _flags(p):
                    help="hidden widths of a Dense stack, e.g. 64,16,64 (18 in, 18 out; tanh / relu alternate, relu "
                         "last): trains an nn.Sequential instead of the 18-14-7-7-18 autoencoder and saves a Keras "
                         ".h5 that `serve --model dense` accepts; with it, predict loads the file as such a stack")
+    p.add_argument("--engine", default="auto", choices=["auto", "persistent", "layers", "throughput"],
+                   help="with --layers: the trainer nn.Model.fit runs; throughput is the large-batch step (two "
+                        "launches per step, any batch size), which trains on the first --take batches held as "
+                        "one array, in the stream's order")
     p.add_argument("--precision", default=None, choices=["fp32", "bf16"],
                    help="small-batch trainer contractions (Keras batch <= 128): fp32 (Keras-exact, default) or "
                         "bf16 MFMAs with fp32 master weights / Adam (compile(minibatch_precision=...))")
@@ -118,7 +122,12 @@ def _train_layers(ns, servers, cfg, epochs, batch_size, out_path):
     model.summary()
     training = _stream(ns, servers, cfg).filter_normal(device=True).normalize()
     t0 = time.perf_counter()
-    model.fit(training, epochs=epochs, batch_size=batch_size, steps_per_epoch=ns.take, verbose=2)
+    shuffle = True
+    if ns.engine == "throughput":   # that engine takes arrays, not a Stream: the epoch's rows, once
+        training = next(iter(training.batch(int(ns.take) * int(batch_size)))).x
+        shuffle = False
+    model.fit(training, epochs=epochs, batch_size=batch_size, steps_per_epoch=ns.take, verbose=2, engine=ns.engine,
+              shuffle=shuffle)
     prec = f", precision {model.last_fit_precision}" if model.last_fit_precision else ""
     print(f"Training complete ({time.perf_counter() - t0:.2f}s, engine {model.last_fit_engine}{prec})", flush=True)
     model.save(out_path)

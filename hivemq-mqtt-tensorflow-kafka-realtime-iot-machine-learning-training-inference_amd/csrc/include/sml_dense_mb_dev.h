@@ -37,8 +37,9 @@ struct Stage {
   float x[SE], y[SE];
 };
 
-template <typename Run>
-__device__ __forceinline__ void stage_load(const DenseMBArgs& a, const Run& run, int O, int s, int k, int steps, Stage& st) {
+// (a: anything with batch, D, ldx and ldy -- DenseMBArgs, or the large-batch step's arguments)
+template <typename Args, typename Run>
+__device__ __forceinline__ void stage_load(const Args& a, const Run& run, int O, int s, int k, int steps, Stage& st) {
   const int r = threadIdx.x / LPR, q = threadIdx.x % LPR;
   int rows = 0;
   int64_t pos = 0;

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "sml_dense_batch.h"
 #include "sml_dense_fleet_serve.h"
 #include "sml_dense_fleet_fwd.h"
 #include "sml_dense_fwd_plan.h"
@@ -419,6 +420,49 @@ hipError_t dense_mb_fleet_launch(DenseMBArgs args, const DenseMBFleetModel* mode
                                  int64_t stride, hipStream_t stream);
 hipError_t dense_mb_fleet_launch_bf16(const DenseMBArgs& args, const DenseMBFleetModel* models, const int32_t* sched,
                                       int M, int64_t stride, hipStream_t stream);   // args checked by dense_mb_fleet_launch
+
+// ---- large-batch train step of a Dense stack (dense_batch.hip): two launches, no host synchronisation ----
+// dense_batch_grad_launch: G workgroups, each the whole bf16 chunk body (sml_dense_mb_bf16_dev.h) over
+// its contiguous span of the step's 32-row chunks, gradients accumulated in registers / LDS, written
+// once as slab[g][nflat] (FlatParams order) and pairs[g] = (loss share incl. penalties, correct rows).
+// The step is rows row0 .. row0 + batch - 1 of `order` (or of x); the divisors are the whole batch's.
+// The limits and the split are in sml_dense_batch.h (plain C++).
+struct DenseBatchArgs {
+  const float* flat;   // fp32 masters, 16-byte aligned, read only
+  const float* x;
+  int64_t ldx;
+  const float* y;      // null: y = x
+  int64_t ldy;
+  const int32_t* order;
+  int64_t n, row0;     // samples; the step's first
+  int batch;           // rows of THIS step, row0 + batch <= n
+  int nl, D;
+  int nflat;           // floats of flat and of a slab; a multiple of 4
+  DenseMBLayer L[DMB_MAXLAYERS];
+  float* slab;         // [G][nflat], zero where no parameter lives
+  float* pairs;        // [G][2]
+};
+hipError_t dense_batch_grad_launch(const DenseBatchArgs& args, int G, hipStream_t stream);
+// dense_batch_apply_launch: elementwise over nflat; sums slab[0 .. G - 1] and the pairs in ascending g,
+// then either applies sml_adam.h in place at step *iter0 + step + 1 and stores that count in *iter
+// (iter0: the count before the call's first step, a copy the kernels never write), or, with flat
+// null, writes the summed gradient to grad_out.  out[0 .. 1] = the step's (mean loss, correct rows).
+struct DenseBatchApplyArgs {
+  const float* slab;
+  const float* pairs;
+  int G, nflat;
+  float* flat;         // null: no update, grad_out instead
+  float* m;
+  float* v;
+  int64_t* iter;
+  const int64_t* iter0;
+  int step;
+  float lr, beta1, beta2, eps;
+  float* grad_out;
+  float* out;
+};
+hipError_t dense_batch_apply_launch(const DenseBatchApplyArgs& args, hipStream_t stream);
+int dense_batch_cus();   // of the current device
 
 // ---- fused bulk forward of a Dense stack (dense_forward.hip) ----
 // One launch runs the whole stack over n rows: rows are read once, activations chain from layer to

@@ -1399,11 +1399,11 @@ struct DenseMBWords {
 // What the two bindings share, in two parts.  The rows: the check of the table against nflat floats of
 // parameters, the table into a.L, the checks of x, y and order against it, and the fields that come
 // from them.  n / row0 / nsteps / lr / out are the caller's.
-static sml::DenseMBArgs dense_mb_rows(const DenseMBWords& w, const std::vector<std::vector<double>>& table, int64_t nflat,
-                                      const at::Tensor& x, const c10::optional<at::Tensor>& y,
+// why: the answer of the caller's check (dense_mb_check here, dense_batch_check for the large-batch step)
+static sml::DenseMBArgs dense_mb_rows(const DenseMBWords& w, const std::vector<std::vector<double>>& table,
+                                      const std::string& why, const at::Tensor& x, const c10::optional<at::Tensor>& y,
                                       const c10::optional<at::Tensor>& order, int64_t batch, int64_t precision) {
   sml::DenseMBArgs a{};
-  const std::string why = dense_mb_check(table, batch, nflat, y.has_value(), precision);
   TORCH_CHECK(why.empty(), w.who, ": ", why);
   a.nl = dense_mb_table(table, a.L);
   a.D = a.L[0].in;
@@ -1456,8 +1456,9 @@ at::Tensor dense_mb_train(const at::Tensor& flat, const at::Tensor& m, const at:
   TORCH_CHECK(iter.is_cuda() && iter.scalar_type() == at::kLong && iter.numel() == 1, "iter must be a device int64[1]");
   TORCH_CHECK(flat.is_contiguous() && m.is_contiguous() && v.is_contiguous() && m.numel() == flat.numel() &&
                   v.numel() == flat.numel(), "flat / m / v must be contiguous and of one size");
-  sml::DenseMBArgs a = dense_mb_rows({"dense_mb_train", "n", "permutation of the n samples"}, table, flat.numel(), x, y,
-                                     order, batch, precision);
+  sml::DenseMBArgs a = dense_mb_rows({"dense_mb_train", "n", "permutation of the n samples"}, table,
+                                     dense_mb_check(table, batch, flat.numel(), y.has_value(), precision), x, y, order,
+                                     batch, precision);
   dense_mb_state(a, flat, m, v, iter, beta1, beta2, eps);
   const int64_t n = x.size(0);
   TORCH_CHECK(nsteps >= 1 && nsteps < (1 << 30) && row0 >= 0 && row0 < n, "bad nsteps / row0");
@@ -1496,7 +1497,8 @@ at::Tensor dense_mb_train_fleet(const at::Tensor& flat, const at::Tensor& m, con
               "iter must be a device int64[", M, "]");
   // the table is checked against stride floats: every parameter offset then lies inside a model's segment
   sml::DenseMBArgs a = dense_mb_rows({"dense_mb_train_fleet", "N", "[N] of indices local to each model's rows"}, table,
-                                     stride, x, y, order, batch, precision);
+                                     dense_mb_check(table, batch, stride, y.has_value(), precision), x, y, order, batch,
+                                     precision);
   dense_mb_state(a, flat, m, v, iter, beta1, beta2, eps);
   const int64_t N = x.size(0);
   TORCH_CHECK(!models.is_cuda() && models.scalar_type() == at::kLong && models.is_contiguous() && models.dim() == 2 &&
@@ -1532,6 +1534,128 @@ at::Tensor dense_mb_train_fleet(const at::Tensor& flat, const at::Tensor& m, con
   SML_CHECK_HIP(sml::dense_mb_fleet_launch(a, reinterpret_cast<const sml::DenseMBFleetModel*>(models_d.data_ptr<int64_t>()),
                                            sched_d.data_ptr<int32_t>(), (int)M, stride, cur_stream(x)));
   return out;
+}
+
+// Empty when dense_batch.hip can run a step of this batch on the stack, else the limit it exceeds.
+std::string dense_batch_check(const std::vector<std::vector<double>>& table, int64_t batch, int64_t nflat,
+                              bool own_targets) {
+  if (table.empty() || table.size() > (size_t)sml::DMB_MAXLAYERS) return dense_mb_check(table, 1, nflat, own_targets, sml::DMB_BF16);
+  sml::DenseMBLayer L[sml::DMB_MAXLAYERS] = {};
+  const int nl = dense_mb_table(table, L);
+  return sml::dense_batch_check(L, nl, L[0].in, batch, nflat < 0 ? INT64_MAX : nflat, own_targets);
+}
+
+// What dense_batch_train and dense_batch_grad share: the checks, the gradient launch's arguments (row0
+// and batch are set per step), the slab buffer [G][nflat] and the pairs [G][2], allocated once per call
+// for the largest step, and the sequence of a step's launches.
+struct DenseBatchCall {
+  sml::DenseBatchArgs g{};
+  sml::DenseBatchApplyArgs ap{};
+  at::Tensor slab, pairs;
+  int groups = 0, cus = 0;
+  int64_t batch = 0;
+
+  DenseBatchCall(const char* who, const at::Tensor& flat, const std::vector<std::vector<double>>& table,
+                 const at::Tensor& x, const c10::optional<at::Tensor>& y, const c10::optional<at::Tensor>& order,
+                 int64_t row0, int64_t batch_, int64_t groups_) {
+    check_dev(flat, "flat", at::kFloat);
+    check_dev(x, "x", at::kFloat);
+    TORCH_CHECK(flat.is_contiguous() && flat.numel() % 4 == 0 && flat.numel() < (1 << 30) &&
+                    reinterpret_cast<uintptr_t>(flat.data_ptr<float>()) % 16 == 0,
+                who, ": flat must be contiguous, 16-byte aligned and a multiple of 4 floats long");
+    const sml::DenseMBArgs r = dense_mb_rows({who, "n", "permutation of the n samples"}, table,
+                                             dense_batch_check(table, batch_, flat.numel(), y.has_value()), x, y, order,
+                                             batch_, sml::DMB_BF16);
+    const int64_t n = x.size(0);
+    TORCH_CHECK(row0 >= 0 && row0 < n, who, ": row0 ", row0, " is outside the ", n, " rows of x");
+    TORCH_CHECK(groups_ >= 0 && groups_ < (1 << 30), who, ": bad groups ", groups_);
+    g.flat = flat.data_ptr<float>();
+    g.x = r.x;
+    g.ldx = r.ldx;
+    g.y = r.y;
+    g.ldy = r.ldy;
+    g.order = r.order;
+    g.n = n;
+    g.nl = r.nl;
+    g.D = r.D;
+    g.nflat = (int)flat.numel();
+    std::copy(r.L, r.L + sml::DMB_MAXLAYERS, g.L);
+    batch = batch_;
+    groups = (int)groups_;
+    cus = sml::dense_batch_cus();
+    const int G = sml::dense_batch_groups((int)std::min(batch, n - row0), groups, cus);
+    slab = at::zeros({G, flat.numel()}, flat.options());
+    pairs = at::zeros({G, 2}, flat.options());
+    g.slab = slab.data_ptr<float>();
+    g.pairs = pairs.data_ptr<float>();
+    ap.slab = g.slab;
+    ap.pairs = g.pairs;
+    ap.nflat = g.nflat;
+  }
+
+  // the two launches of the step that starts at sample r0; ap's targets are the caller's
+  void step(int64_t r0, hipStream_t stream) {
+    g.row0 = r0;
+    g.batch = (int)std::min(batch, g.n - r0);
+    ap.G = sml::dense_batch_groups(g.batch, groups, cus);
+    SML_CHECK_HIP(sml::dense_batch_grad_launch(g, ap.G, stream));
+    SML_CHECK_HIP(sml::dense_batch_apply_launch(ap, stream));
+  }
+};
+
+// nsteps consecutive Keras steps of a Dense stack at any batch up to 2^24 (dense_batch.hip): 2 * nsteps
+// launches on the current stream, no host synchronisation; flat / m / v / iter are updated in place;
+// returns [nsteps, 2] = (mean loss incl. penalties, rows with matching argmax).  groups: workgroups of
+// a step (0: one per CU), clamped to the step's 32-row chunks.
+at::Tensor dense_batch_train(const at::Tensor& flat, const at::Tensor& m, const at::Tensor& v, const at::Tensor& iter,
+                             const std::vector<std::vector<double>>& table, const at::Tensor& x,
+                             const c10::optional<at::Tensor>& y, const c10::optional<at::Tensor>& order, int64_t row0,
+                             int64_t batch, int64_t nsteps, double lr, double beta1, double beta2, double eps,
+                             int64_t groups) {
+  check_dev(m, "m", at::kFloat);
+  check_dev(v, "v", at::kFloat);
+  TORCH_CHECK(iter.is_cuda() && iter.scalar_type() == at::kLong && iter.numel() == 1, "iter must be a device int64[1]");
+  TORCH_CHECK(m.is_contiguous() && v.is_contiguous() && m.numel() == flat.numel() && v.numel() == flat.numel(),
+              "flat / m / v must be contiguous and of one size");
+  TORCH_CHECK(nsteps >= 1 && nsteps < (1 << 30), "bad nsteps");
+  check_dev(x, "x", at::kFloat);
+  c10::hip::HIPGuard guard(x.device().index());
+  DenseBatchCall call("dense_batch_train", flat, table, x, y, order, row0, batch, groups);
+  auto out = at::zeros({nsteps, 2}, flat.options());
+  const at::Tensor iter0 = iter.clone();   // the count before the first step: no launch writes it
+  call.ap.flat = flat.data_ptr<float>();
+  call.ap.m = m.data_ptr<float>();
+  call.ap.v = v.data_ptr<float>();
+  call.ap.iter = iter.data_ptr<int64_t>();
+  call.ap.iter0 = iter0.data_ptr<int64_t>();
+  call.ap.lr = (float)lr;
+  call.ap.beta1 = (float)beta1;
+  call.ap.beta2 = (float)beta2;
+  call.ap.eps = (float)eps;
+  const int64_t steps = std::min(nsteps, (call.g.n - row0 + batch - 1) / batch);
+  for (int64_t s = 0; s < steps; ++s) {
+    call.ap.step = (int)s;
+    call.ap.out = out.data_ptr<float>() + 2 * s;
+    call.step(row0 + s * batch, cur_stream(x));
+  }
+  return out;
+}
+
+// One step's summed gradient [nflat] (FlatParams order) and its [mean loss, correct rows], parameters
+// untouched: dense_batch_train's two launches with the update switched off.
+std::tuple<at::Tensor, at::Tensor> dense_batch_grad(const at::Tensor& flat, const std::vector<std::vector<double>>& table,
+                                                    const at::Tensor& x, const c10::optional<at::Tensor>& y,
+                                                    const c10::optional<at::Tensor>& order, int64_t row0, int64_t batch,
+                                                    int64_t groups) {
+  check_dev(x, "x", at::kFloat);
+  c10::hip::HIPGuard guard(x.device().index());
+  DenseBatchCall call("dense_batch_grad", flat, table, x, y, order, row0, batch, groups);
+  auto grad = at::zeros({flat.numel()}, flat.options());
+  auto out = at::zeros({2}, flat.options());
+  call.ap.grad_out = grad.data_ptr<float>();
+  call.ap.out = out.data_ptr<float>();
+  call.step(row0, cur_stream(x));
+  return std::make_tuple(grad, out);
 }
 
 // Fused LSTM Dense head (lstm_head.hip): returns dh = dy . W^T as bf16 [n, 16]; dW / db into grad
@@ -2158,6 +2282,20 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "empty if dense_mb_train can run the table at this batch and precision (0 fp32, 1 bf16), else the reason",
         py::arg("table"), py::arg("batch"), py::arg("nflat") = -1, py::arg("own_targets") = false,
         py::arg("precision") = 0);
+  m.def("dense_batch_train", &dense_batch_train,
+        "large-batch trainer: nsteps Keras Adam steps of a Dense stack (dense_mb_train's table) at any batch up to "
+        "2^24, two launches per step on bf16 MFMAs; groups: workgroups of a step (0: one per CU)",
+        py::arg("flat"), py::arg("m"), py::arg("v"), py::arg("iter"), py::arg("table"), py::arg("x"),
+        py::arg("y") = py::none(), py::arg("order") = py::none(), py::arg("row0") = 0, py::arg("batch") = 1024,
+        py::arg("nsteps") = 1, py::arg("lr") = 1e-3, py::arg("beta1") = 0.9, py::arg("beta2") = 0.999,
+        py::arg("eps") = 1e-7, py::arg("groups") = 0);
+  m.def("dense_batch_grad", &dense_batch_grad,
+        "one step of dense_batch_train without the update -> (summed gradient [nflat], [mean loss, correct rows])",
+        py::arg("flat"), py::arg("table"), py::arg("x"), py::arg("y") = py::none(), py::arg("order") = py::none(),
+        py::arg("row0") = 0, py::arg("batch") = 1024, py::arg("groups") = 0);
+  m.def("dense_batch_check", &dense_batch_check,
+        "empty if dense_batch_train can run the table at this batch, else the reason", py::arg("table"),
+        py::arg("batch"), py::arg("nflat") = -1, py::arg("own_targets") = false);
   m.def("dense_mb_train_fleet", &dense_mb_train_fleet,
         "one launch for M Dense stacks of one architecture, one workgroup per model: flat / m / v [M, stride], iter [M], "
         "host descriptors models [M, 4] int64 and schedule sched [M] int32 -> [M, max nsteps, 2]",
@@ -2204,6 +2342,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.attr("DMB_MAXPARAMS") = (int)sml::DMB_MAXPARAMS;
   m.attr("DMB_MAXPARAMS_BF16") = (int)sml::DMB_MAXPARAMS_BF16;
   m.attr("DMB_LDS_BYTES") = (int)sml::DMB_LDS_BYTES;
+  m.attr("DBT_MAXBATCH") = (int)sml::DBT_MAXBATCH;
   m.def("mlp_fwd", &mlp_fwd, "dropout(act(x . W + b)) on fp32 MFMA (x float32 or uint8 scaled by 1/255)",
         py::arg("x"), py::arg("W"), py::arg("b") = py::none(), py::arg("relu") = false, py::arg("keep") = 1.0,
         py::arg("seed") = 0, py::arg("step") = 0);

@@ -424,11 +424,18 @@ class Model:
         the trained state), as ``compile(fused=False)`` does for every call.  ``last_fit_engine`` records the choice,
         and ``last_fit_precision`` the persistent trainer's kernel (``"bf16"`` when
         ``compile(minibatch_precision="bf16")`` asked for it and the stack fits the bf16 kernel, else
-        ``"fp32"``; ``None`` when another engine ran)."""
-        if engine not in ("auto", "persistent", "layers"):
-            raise ValueError(f"engine must be 'auto', 'persistent' or 'layers', not {engine!r}")
+        ``"fp32"``; ``None`` when another engine ran).  ``"throughput"`` runs the large-batch step
+        (``ops.dense_batch``: two launches per step on bf16 MFMAs, any batch up to its ``MAX_BATCH``,
+        the layer loop's shuffled batches) and raises ``ValueError`` with the reason if it cannot:
+        a limit of the stack, no ROCm device, several ranks, a ``Stream`` input, or the recognised
+        autoencoder, which has a throughput engine of its own; ``"auto"`` never picks it."""
+        if engine not in ("auto", "persistent", "layers", "throughput"):
+            raise ValueError(f"engine must be 'auto', 'persistent', 'layers' or 'throughput', not {engine!r}")
         if not self.compiled:
             self.compile()
+        if self._fused is not None and engine == "throughput":
+            raise ValueError("engine='throughput' cannot run: this model is the recognised 4-layer autoencoder, "
+                             "which has its own throughput engine (models.Autoencoder.fit)")
         if self._fused is not None and engine == "persistent":
             raise ValueError("engine='persistent' cannot run: this model is the recognised 4-layer autoencoder, "
                              "which trains on the fused kernel")
@@ -447,6 +454,12 @@ class Model:
         world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
         rank = dist.get_rank() if world > 1 else 0
         allreduce = allreduce_sum_ if world > 1 else None
+        if engine == "throughput":
+            why = self._persistent_reason(x, y, batch_size, world, throughput=True)
+            if why:
+                raise ValueError(f"engine='throughput' cannot run: {why}")
+            return self._fit_persistent(x, y, batch_size, epochs, verbose, callbacks, validation_data, shuffle,
+                                        steps_per_epoch, seed, initial_epoch, throughput=True)
         if engine != "layers":
             why = self._persistent_reason(x, y, batch_size, world)
             if not why and engine == "auto" and self._fused_arg is False:
@@ -514,21 +527,24 @@ class Model:
     # rows of a Stream staged on the device per launch (rounded down to a multiple of the batch)
     STREAM_SEGMENT_ROWS = 1 << 18
 
-    def _persistent_reason(self, x, y, batch_size, world) -> str:
-        """Empty if ``ops.dense_persistent`` can run this fit, else why not."""
+    def _persistent_reason(self, x, y, batch_size, world, throughput: bool = False) -> str:
+        """Empty if ``ops.dense_persistent`` (``throughput``: ``ops.dense_batch``) can run this fit,
+        else why not."""
         from ..data.stream import Stream
-        from ..ops import dense_persistent as dpers
+        from ..ops import dense_batch, dense_persistent as dpers
         if self.device.type != "cuda":
             return "it needs a ROCm device"
         if world > 1:
             return "torch.distributed training stays on the layer engine"
         own_targets = y is not None and y is not x
         if isinstance(x, Stream):
+            if throughput:
+                return "a Stream input trains on the other engines"
             if own_targets:
                 return "a Stream carries no targets of its own"
         elif not isinstance(x, (np.ndarray, torch.Tensor, list, tuple)):
             return "the input must be arrays, tensors or a Stream"
-        ok, why = dpers.supports(self, batch_size, own_targets=own_targets)
+        ok, why = (dense_batch if throughput else dpers).supports(self, batch_size, own_targets=own_targets)
         if not ok:
             return why
         if not isinstance(x, Stream):
@@ -542,19 +558,21 @@ class Model:
         return ""
 
     def _fit_persistent(self, x, y, batch_size, epochs, verbose, callbacks, validation_data, shuffle,
-                        steps_per_epoch, seed, initial_epoch) -> History:
+                        steps_per_epoch, seed, initial_epoch, throughput: bool = False) -> History:
         """One ``dense_minibatch`` launch per epoch (per segment of a Stream); the kernel updates
-        ``fp.flat / m / v / iter`` in place, so save / predict / evaluate see the trained state."""
+        ``fp.flat / m / v / iter`` in place, so save / predict / evaluate see the trained state.
+        ``throughput``: one ``ops.dense_batch.train_steps`` call per epoch instead (arrays only)."""
         from ..data.stream import Stream
-        from ..ops import dense_persistent as dpers
+        from ..ops import dense_batch, dense_persistent as dpers
         from ..parallel.fault import maybe_inject_range
-        self.last_fit_engine = "persistent"
+        self.last_fit_engine = "throughput" if throughput else "persistent"
         B = int(batch_size)
         stream = isinstance(x, Stream)
         # bf16 only where it was asked for and the stack fits the bf16 kernel; never an error
         own_targets = not stream and y is not None and y is not x
         prec = "fp32"
-        if self.minibatch_precision == "bf16" and dpers.supports(self, B, own_targets=own_targets, precision="bf16")[0]:
+        if throughput or (self.minibatch_precision == "bf16" and
+                          dpers.supports(self, B, own_targets=own_targets, precision="bf16")[0]):
             prec = "bf16"
         self.last_fit_precision = prec
         if not stream:
@@ -603,7 +621,10 @@ class Model:
                     order = torch.from_numpy(rng.permutation(n).astype(np.int32)).to(self.device)
                 if steps > 0:
                     maybe_inject_range(gstep, gstep + steps, 0)
-                    results.append(dpers.train_steps(self, xd, yd, B, steps, 0, order, precision=prec))
+                    if throughput:
+                        results.append(dense_batch.train_steps(self, xd, yd, B, steps, 0, order))
+                    else:
+                        results.append(dpers.train_steps(self, xd, yd, B, steps, 0, order, precision=prec))
                 rows = min(n, steps * B)
                 weights = [B] * (steps - 1) + [rows - B * (steps - 1)] if steps > 0 else []
                 gstep += steps

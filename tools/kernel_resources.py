@@ -30,6 +30,8 @@ def main():
         vgpr_form = [] if "sml-build: agpr-accumulators" in head else ["-mllvm", "-amdgpu-mfma-vgpr-form"]
         if "sml-build: no-slp" in head:
             vgpr_form += ["-fno-slp-vectorize"]
+        if "sml-build: no-packed-fp32" in head:
+            vgpr_form += ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
     cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-munsafe-fp-atomics", *vgpr_form,
            "-I", os.path.join(PKG, "csrc", "include"), "-c", src, "-o", "/dev/null",
            "--offload-device-only", "-Rpass-analysis=kernel-resource-usage"]
