@@ -54,6 +54,10 @@ def _flags(p):
                    help="with --layers: the trainer nn.Model.fit runs; throughput is the large-batch step (two "
                         "launches per step, any batch size), which trains on the first --take batches held as "
                         "one array, in the stream's order")
+    p.add_argument("--predict-engine", default="auto", choices=["auto", "fused", "layers", "wide"],
+                   help="predict --layers: the forward nn.Model.predict runs; fused is the fp32 one-launch kernel "
+                        "(widths up to 128), wide the bf16 one (widths up to 512), layers the layer loop; fused and "
+                        "wide fail with the reason when they cannot run")
     p.add_argument("--precision", default=None, choices=["fp32", "bf16"],
                    help="small-batch trainer contractions (Keras batch <= 128): fp32 (Keras-exact, default) or "
                         "bf16 MFMAs with fp32 master weights / Adam (compile(minibatch_precision=...))")
@@ -155,8 +159,12 @@ def _predict(ns, servers, cfg, model, batch_size, result_topic):
     if result_topic:
         sink = KafkaPredictionSink(batch_size, result_topic, servers, cfg, with_score=ns.with_score)
         cbs.append(sink)
-    out = model.predict(data, batch_size=batch_size, callbacks=cbs)
-    eng = getattr(model, "last_predict_engine", None)   # nn.Model (--layers): "fused" | "layers"
+    engine = getattr(ns, "predict_engine", "auto")
+    if engine != "auto" and not ns.layers:
+        raise SystemExit("--predict-engine chooses the forward of a --layers stack")
+    kw = {"engine": engine} if ns.layers else {}
+    out = model.predict(data, batch_size=batch_size, callbacks=cbs, **kw)
+    eng = getattr(model, "last_predict_engine", None)   # nn.Model (--layers): "fused" | "layers" | "wide"
     print(f"predict {out.shape[0]} events -> {result_topic}" + (f" (engine {eng})" if eng else ""), flush=True)
     print("Predict complete", flush=True)
     return out

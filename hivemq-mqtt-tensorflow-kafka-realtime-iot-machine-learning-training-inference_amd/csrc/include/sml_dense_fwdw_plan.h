@@ -1,0 +1,123 @@
+// The fused bulk forward of WIDE Dense stacks (kernels/dense_forward_wide.hip): its limits, its layer
+// table, the offsets of the packed bf16 weight image, its LDS plan and the check that names the limit a
+// stack exceeds.  Plain C++17 with no HIP header, in the manner of sml_dense_fwd_plan.h.
+// ops/dense_forward_wide.py mirrors the check and the plan in Python, because supports() must answer
+// without a built extension.
+//
+// IMAGE (16-bit words; offsets in words).  Per layer, blocks of 32 inputs (kb) by 16 units (ub) in the
+// order of a v_mfma_f32_16x16x32_bf16 A fragment:
+//   img[w_off + ((kb * nub + ub) * 64 + lane) * 8 + j] = bf16(W[32 kb + 8 (lane / 16) + j][16 ub + lane % 16])
+// zero past `in` and `out`, so a lane fetches its eight k-values of a (kb, ub) block with one 16-byte
+// load; then the layer's bias as fp32 [16 nub] (two words each), zero past `out` (all zero for a layer
+// without bias).  Every offset is a multiple of 8 words: 16-byte loads stay aligned.
+#pragma once
+
+#include <cstdint>
+#include <string>
+
+namespace sml {
+
+enum : int {
+  DFWW_MAXLAYERS = 8,
+  DFWW_MAXW = 512,             // units / inputs of a layer
+  DFWW_WAVES = 8,              // waves of a workgroup; wave w owns the unit blocks w, w + 8, w + 16, w + 24
+  DFWW_MAXUB = 4,              // unit blocks a wave owns at most: DFWW_MAXW / 16 / DFWW_WAVES
+  DFWW_ROWS_SMALL = 64,        // rows of a workgroup's tile: 4 or 8 MFMA row tiles
+  DFWW_ROWS_LARGE = 128,
+  DFWW_ROW_PAD = 8,            // words added to an activation row in LDS (16-byte aligned, off the bank stride)
+  DFWW_PART_WORDS = 5,         // a wave's epilogue partial of a row: squared error, (max, argmax) of y and of the target
+  DFWW_LDS_BYTES = 160 * 1024,
+  DFWW_STATIC_LDS = 2048,      // the kernel's own static LDS
+  DFWW_ACT_LAST = 3            // activation codes 0 .. 3 (Act of sml_common.h: ACT_LINEAR .. ACT_SIGMOID)
+};
+static_assert(DFWW_MAXUB * DFWW_WAVES * 16 == DFWW_MAXW, "a wave's accumulators hold its whole unit slice");
+
+struct DenseFwdWLayer {
+  int in, out;
+  int act;             // ACT_* code
+  int w_off, b_off;    // word offsets of the layer's blocks and of its padded fp32 bias in the image
+};
+
+struct DenseFwdWPlan {
+  int img_words;
+  int rows;            // rows of a tile (DFWW_ROWS_SMALL or DFWW_ROWS_LARGE)
+  int stride;          // words between two activation rows in LDS
+  int lds_bytes;       // dynamic LDS: the activation tile, which the epilogue's partials reuse
+};
+
+constexpr int dfww_pad16(int n) { return (n + 15) / 16 * 16; }
+constexpr int dfww_pad32(int n) { return (n + 31) / 32 * 32; }
+
+// fills w_off / b_off from in / out; returns the words of the image
+inline int dense_fwdw_image_offsets(DenseFwdWLayer* L, int nl) {
+  int off = 0;
+  for (int l = 0; l < nl; ++l) {
+    L[l].w_off = off;
+    off += dfww_pad32(L[l].in) * dfww_pad16(L[l].out);
+    L[l].b_off = off;
+    off += 2 * dfww_pad16(L[l].out);
+  }
+  return off;
+}
+
+// tile == 0: the kernel's own choice of the rows of a tile for n rows on `cus` CUs.  One workgroup
+// runs per CU either way (153 / 229 VGPRs); the large tile fetches each weight fragment half as often
+// per row, the small one fills the CUs from half as many rows.
+inline int dense_fwdw_rows(int64_t n, int cus, int tile) {
+  if (tile == DFWW_ROWS_SMALL || tile == DFWW_ROWS_LARGE) return tile;
+  return n >= (int64_t)DFWW_ROWS_LARGE * cus ? DFWW_ROWS_LARGE : DFWW_ROWS_SMALL;
+}
+
+inline DenseFwdWPlan dense_fwdw_plan(const DenseFwdWLayer* L, int nl, int rows) {
+  DenseFwdWPlan P{};
+  int kmax = 0, off = 0;
+  for (int l = 0; l < nl; ++l) {
+    const int kp = dfww_pad32(L[l].in), np = dfww_pad16(L[l].out);
+    kmax = kp > kmax ? kp : kmax;
+    off += kp * np + 2 * np;
+  }
+  P.img_words = off;
+  P.rows = rows;
+  P.stride = kmax + DFWW_ROW_PAD;
+  const int act = rows * P.stride * 2, part = DFWW_WAVES * rows * DFWW_PART_WORDS * 4;
+  P.lds_bytes = act > part ? act : part;
+  return P;
+}
+// the widest plan fits: LDS never refuses a stack inside the width limit
+static_assert(DFWW_ROWS_LARGE * (DFWW_MAXW + DFWW_ROW_PAD) * 2 + DFWW_STATIC_LDS <= DFWW_LDS_BYTES, "LDS plan");
+
+// empty if the kernel takes the stack (D inputs, nl layers whose image offsets lie inside img_words
+// words, or anywhere if that is negative; score: the target is the input row, so out == D), else the
+// limit it exceeds
+inline std::string dense_fwdw_check(const DenseFwdWLayer* L, int nl, int D, int64_t img_words, bool score) {
+  using std::to_string;
+  if (nl < 1 || nl > DFWW_MAXLAYERS)
+    return to_string(nl) + " Dense layers: the wide fused forward takes 1.." + to_string(DFWW_MAXLAYERS) + " (MAX_LAYERS)";
+  if (D < 1 || D > DFWW_MAXW)
+    return "input width " + to_string(D) + " is outside 1.." + to_string(DFWW_MAXW) + " (MAX_WIDTH)";
+  int prev = D;
+  for (int l = 0; l < nl; ++l) {
+    if (L[l].in != prev) return "layer " + to_string(l) + " does not take the previous layer's width";
+    if (L[l].out < 1 || L[l].out > DFWW_MAXW)
+      return "layer " + to_string(l) + " has " + to_string(L[l].out) + " units: the limit is " + to_string(DFWW_MAXW) +
+             " (MAX_WIDTH)";
+    if (L[l].act < 0 || L[l].act > DFWW_ACT_LAST) return "layer " + to_string(l) + ": unknown activation";
+    prev = L[l].out;
+  }
+  if (score && prev != D)
+    return "scores against the input row need as many output units as inputs (" + to_string(prev) + " units, " +
+           to_string(D) + " inputs)";
+  if (img_words >= 0) {
+    DenseFwdWLayer T[DFWW_MAXLAYERS];
+    for (int l = 0; l < nl; ++l) T[l] = L[l];
+    const int want = dense_fwdw_image_offsets(T, nl);
+    if (img_words != want)
+      return "an image of " + to_string(img_words) + " words: the stack packs into " + to_string(want);
+    for (int l = 0; l < nl; ++l)
+      if (L[l].w_off != T[l].w_off || L[l].b_off != T[l].b_off)
+        return "layer " + to_string(l) + ": image offsets are not those of the packed layout";
+  }
+  return "";
+}
+
+}  // namespace sml

@@ -7,6 +7,7 @@
 #include "sml_dense_fleet_serve.h"
 #include "sml_dense_fleet_fwd.h"
 #include "sml_dense_fwd_plan.h"
+#include "sml_dense_fwdw_plan.h"
 #include "sml_dense_mb_plan.h"
 
 namespace sml {
@@ -530,6 +531,36 @@ struct DenseFleetFwdArgs {
 // workgroups dense_fleet_fwd_launch starts for `pairs` >= 1 tile pairs
 int dense_fleet_fwd_grid(const DenseFwdLayer* L, int nl, int D, int64_t pairs, int max_blocks);
 hipError_t dense_fleet_fwd_launch(const DenseFleetFwdArgs& args, hipStream_t stream);
+
+// ---- fused bulk forward of a WIDE Dense stack, widths up to 512 (dense_forward_wide.hip) ----
+// The outputs of dense_fwd_launch with the rounding points of the bf16 trainers' forward: every
+// contraction is bf16(h) . bf16(W) on v_mfma_f32_16x16x32_bf16 with fp32 accumulation, bias, activation,
+// scores and sums in fp32 / double.  Weights stream from a bf16 image in device memory (L2), a tile's
+// activations stay in LDS.  The limits, DenseFwdWLayer, the image layout, the LDS plan and
+// dense_fwdw_check are in sml_dense_fwdw_plan.h (plain C++).
+struct DenseFwdWArgs {
+  const float* x;          // [n, D] rows, features contiguous
+  int64_t ldx;
+  int64_t n;
+  const uint16_t* image;   // 16-byte aligned
+  int img_words;
+  const float* scale;      // [D] or null
+  const float* shift;
+  float* rec;              // [n, out] contiguous, or null
+  float* score;            // [n] or null
+  uint8_t* flag;           // [n] or null (needs score)
+  float threshold;
+  double* sums;            // [grid][2] or null
+  const float* y;          // own targets of sums, or null
+  int64_t ldy;
+  int nl, D;
+  int max_blocks;          // 0: as many workgroups as the CUs hold
+  int tile;                // rows of a workgroup's tile: 64, 128 or 0 (the kernel's choice)
+  DenseFwdWLayer L[DFWW_MAXLAYERS];
+};
+// workgroups dense_fwdw_launch starts for n >= 1 rows of a stack that passes dense_fwdw_check
+int dense_fwdw_grid(const DenseFwdWLayer* L, int nl, int64_t n, int max_blocks, int tile);
+hipError_t dense_fwdw_launch(const DenseFwdWArgs& args, hipStream_t stream);
 
 // ---- fused MSE + categorical accuracy (loss.hip) ----
 bool mse_acc_supported(int F);

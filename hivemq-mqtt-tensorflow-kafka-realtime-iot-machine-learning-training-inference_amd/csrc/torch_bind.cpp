@@ -1240,6 +1240,105 @@ c10::optional<at::Tensor> dense_forward(const at::Tensor& x, const at::Tensor& i
   return part;
 }
 
+// ---- the wide variant (dense_forward_wide.hip, sml_dense_fwdw_plan.h) ----
+// Table rows: (in, units, act, w_off, b_off), offsets in 16-bit words of the bf16 image.
+static int dense_fwdw_table(const std::vector<std::vector<int64_t>>& table, sml::DenseFwdWLayer* L) {
+  if (table.size() > (size_t)sml::DFWW_MAXLAYERS) return (int)table.size();
+  int nl = 0;
+  for (const auto& t : table) {
+    TORCH_CHECK(t.size() == 5, "layer descriptor: (in, units, act, w_off, b_off)");
+    auto i32 = [](int64_t v) { return (int)std::min<int64_t>(std::max<int64_t>(v, -1), 1 << 30); };
+    L[nl++] = sml::DenseFwdWLayer{i32(t[0]), i32(t[1]), i32(t[2]), i32(t[3]), i32(t[4])};
+  }
+  return nl;
+}
+
+// Empty when dense_forward_wide.hip takes the stack (score: against the input row), else the limit it exceeds.
+std::string dense_fwdw_check(const std::vector<std::vector<int64_t>>& table, int64_t img_words, bool score) {
+  sml::DenseFwdWLayer L[sml::DFWW_MAXLAYERS] = {};
+  const int nl = dense_fwdw_table(table, L);
+  return sml::dense_fwdw_check(L, nl, nl ? L[0].in : 0, img_words, score);
+}
+
+// dense_forward's arguments and results on the wide kernel: image is the bf16 image as int16 words;
+// tile: 64 or 128 rows per workgroup tile, 0 for the kernel's choice.
+c10::optional<at::Tensor> dense_forward_wide(const at::Tensor& x, const at::Tensor& image,
+                                             const std::vector<std::vector<int64_t>>& table,
+                                             const c10::optional<at::Tensor>& scale, const c10::optional<at::Tensor>& shift,
+                                             const c10::optional<at::Tensor>& rec, const c10::optional<at::Tensor>& score,
+                                             const c10::optional<at::Tensor>& flag, double threshold, bool sums,
+                                             const c10::optional<at::Tensor>& y, int64_t max_blocks, int64_t tile) {
+  check_dev(x, "x", at::kFloat);
+  check_dev(image, "image", at::kShort);
+  TORCH_CHECK(image.dim() == 1 && image.is_contiguous(), "image must be a flat int16 tensor");
+  for (const c10::optional<at::Tensor>* t : {&scale, &shift, &rec, &score, &flag, &y})
+    TORCH_CHECK(!t->has_value() || (*t)->device() == x.device(), "every tensor must live on x's device");
+  TORCH_CHECK(image.device() == x.device(), "image must live on x's device");
+  sml::DenseFwdWArgs a{};
+  const bool scored = score.has_value() || (sums && !y.has_value());
+  const std::string why = dense_fwdw_check(table, image.numel(), scored);
+  TORCH_CHECK(why.empty(), "dense_forward_wide: ", why);
+  a.nl = dense_fwdw_table(table, a.L);
+  a.D = a.L[0].in;
+  const int64_t O = a.L[a.nl - 1].out, n = x.dim() == 2 ? x.size(0) : 0;
+  TORCH_CHECK(x.dim() == 2 && n >= 1 && x.size(1) == a.D && (a.D == 1 || x.stride(1) == 1) &&
+                  (n == 1 || x.stride(0) >= a.D),
+              "x must be [n >= 1, ", a.D, "] rows with contiguous features");
+  a.x = x.data_ptr<float>();
+  a.ldx = n == 1 ? a.D : x.stride(0);
+  a.n = n;
+  a.image = reinterpret_cast<const uint16_t*>(image.data_ptr<int16_t>());
+  a.img_words = (int)image.numel();
+  TORCH_CHECK(scale.has_value() == shift.has_value(), "scale and shift come together");
+  if (scale.has_value()) {
+    check_dev(*scale, "scale", at::kFloat);
+    check_dev(*shift, "shift", at::kFloat);
+    TORCH_CHECK(scale->numel() == a.D && shift->numel() == a.D && scale->is_contiguous() && shift->is_contiguous(),
+                "scale / shift must have ", a.D, " entries");
+    a.scale = scale->data_ptr<float>();
+    a.shift = shift->data_ptr<float>();
+  }
+  if (rec.has_value()) {
+    check_dev(*rec, "rec", at::kFloat);
+    TORCH_CHECK(rec->dim() == 2 && rec->size(0) == n && rec->size(1) == O && rec->is_contiguous(), "rec must be a contiguous [n, ",
+                O, "]");
+    a.rec = rec->data_ptr<float>();
+  }
+  if (score.has_value()) {
+    check_dev(*score, "score", at::kFloat);
+    TORCH_CHECK(score->dim() == 1 && score->numel() == n && score->is_contiguous(), "score must be a contiguous [n]");
+    a.score = score->data_ptr<float>();
+  }
+  if (flag.has_value()) {
+    TORCH_CHECK(score.has_value(), "flags need scores");
+    TORCH_CHECK(flag->is_cuda() && (flag->scalar_type() == at::kByte || flag->scalar_type() == at::kBool) && flag->dim() == 1 &&
+                    flag->numel() == n && flag->is_contiguous(), "flag must be a contiguous device uint8 / bool [n]");
+    a.flag = static_cast<uint8_t*>(flag->data_ptr());
+  }
+  a.threshold = (float)threshold;
+  if (y.has_value()) {
+    check_dev(*y, "y", at::kFloat);
+    TORCH_CHECK(sums && !score.has_value(), "own targets are for sums alone");
+    TORCH_CHECK(y->dim() == 2 && y->size(0) == n && y->size(1) == O && (O == 1 || y->stride(1) == 1) &&
+                    (n == 1 || y->stride(0) >= O), "y must be [n, ", O, "] rows with contiguous features");
+    a.y = y->data_ptr<float>();
+    a.ldy = n == 1 ? O : y->stride(0);
+  }
+  TORCH_CHECK(rec.has_value() || score.has_value() || sums, "nothing to compute");
+  TORCH_CHECK(max_blocks >= 0 && max_blocks < (1 << 20), "bad max_blocks");
+  TORCH_CHECK(tile == 0 || tile == sml::DFWW_ROWS_SMALL || tile == sml::DFWW_ROWS_LARGE, "tile must be 0, 64 or 128");
+  a.max_blocks = (int)max_blocks;
+  a.tile = (int)tile;
+  c10::hip::HIPGuard guard(x.device().index());
+  c10::optional<at::Tensor> part;
+  if (sums) {
+    part = at::empty({sml::dense_fwdw_grid(a.L, a.nl, n, a.max_blocks, a.tile), 2}, x.options().dtype(at::kDouble));
+    a.sums = part->data_ptr<double>();
+  }
+  SML_CHECK_HIP(sml::dense_fwdw_launch(a, cur_stream(x)));
+  return part;
+}
+
 // ---- the fleet variant (dense_forward_fleet.hip, sml_dense_fleet_fwd.h) ----
 static const int64_t* fleet_rows_table(const c10::optional<at::Tensor>& t, int64_t M) {
   if (!t.has_value()) return nullptr;
@@ -2313,6 +2412,19 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "empty if dense_forward takes the table (img_floats < 0: offsets unchecked; score: against the input row), "
         "else the limit it exceeds",
         py::arg("table"), py::arg("img_floats") = -1, py::arg("score") = false);
+  m.def("dense_forward_wide", &dense_forward_wide,
+        "dense_forward for stacks up to 512 wide on bf16 MFMAs: image is the bf16 image as int16 words (table offsets "
+        "in words); tile = rows of a workgroup's tile (64, 128, or 0 for the kernel's choice)",
+        py::arg("x"), py::arg("image"), py::arg("table"), py::arg("scale") = py::none(), py::arg("shift") = py::none(),
+        py::arg("rec") = py::none(), py::arg("score") = py::none(), py::arg("flag") = py::none(),
+        py::arg("threshold") = 0.0, py::arg("sums") = false, py::arg("y") = py::none(), py::arg("max_blocks") = 0,
+        py::arg("tile") = 0);
+  m.def("dense_fwdw_check", &dense_fwdw_check,
+        "empty if dense_forward_wide takes the table (img_words < 0: offsets unchecked; score: against the input row), "
+        "else the limit it exceeds",
+        py::arg("table"), py::arg("img_words") = -1, py::arg("score") = false);
+  m.attr("DFWW_MAXLAYERS") = (int)sml::DFWW_MAXLAYERS;
+  m.attr("DFWW_MAXW") = (int)sml::DFWW_MAXW;
   m.def("dense_forward_fleet", &dense_forward_fleet,
         "fused bulk forward of a fleet of Dense stacks in one launch: model m (image images[m]) over rows "
         "table[m] = {first row, rows} of x; writes rec / score / flag (score > thr[m]) where given; sums -> "

@@ -116,7 +116,7 @@ class Model:
         self._fused_arg: Optional[bool] = None
         self.last_fit_engine: Optional[str] = None
         self.last_fit_precision: Optional[str] = None
-        self.last_predict_engine: Optional[str] = None     # "fused" | "layers" | "autoencoder"
+        self.last_predict_engine: Optional[str] = None     # "fused" | "wide" | "layers" | "autoencoder"
         self.last_evaluate_engine: Optional[str] = None
         self.last_score_engine: Optional[str] = None
         self.minibatch_precision: Optional[str] = None
@@ -656,17 +656,22 @@ class Model:
         return hist
 
     # ------------------------------------------------------------------ inference
-    def _bulk_engine(self, what: str, engine: str, x, score: bool = False, need_mse: bool = False) -> bool:
-        """True when the fused bulk forward (``ops.dense_forward``: the whole stack in one launch, fp32)
-        takes this call, False for the layer loop.  ``auto`` takes the kernel when the device is ROCm,
-        the stack is inside its limits and the rows are fp32 (arrays, tensors or a ``Stream``);
-        ``engine="fused"`` raises ``ValueError`` with the reason when it cannot run."""
-        if engine not in ("auto", "fused", "layers"):
-            raise ValueError(f"engine must be 'auto', 'fused' or 'layers', not {engine!r}")
+    def _bulk_engine(self, what: str, engine: str, x, score: bool = False, need_mse: bool = False):
+        """The fused bulk forward that takes this call, or None for the layer loop: ``ops.dense_forward``
+        (the whole stack in one launch, fp32, widths up to 128) or, under ``engine="wide"`` alone,
+        ``ops.dense_forward_wide`` (bf16 MFMAs with the bf16 trainers' rounding points, widths up to 512).
+        ``auto`` takes the fp32 kernel when the device is ROCm, the stack is inside its limits and the rows
+        are fp32 (arrays, tensors or a ``Stream``); it never picks ``"wide"``.  ``engine="fused"`` and
+        ``engine="wide"`` raise ``ValueError`` with the reason when they cannot run."""
+        if engine not in ("auto", "fused", "layers", "wide"):
+            raise ValueError(f"engine must be 'auto', 'fused', 'layers' or 'wide', not {engine!r}")
         if engine == "layers":
-            return False
+            return None
         from ..data.stream import Stream
-        from ..ops import dense_forward as dfw
+        if engine == "wide":
+            from ..ops import dense_forward_wide as dfw
+        else:
+            from ..ops import dense_forward as dfw
         why = ""
         if self.device.type != "cuda":
             why = f"the model is on {self.device}, not on a ROCm device"
@@ -680,9 +685,13 @@ class Model:
                 dt = x.dtype if isinstance(x, torch.Tensor) else np.asarray(x).dtype
                 if dt not in (torch.float32, np.dtype(np.float32)):
                     why = f"rows of dtype {dt}: the kernel reads fp32"
-        if why and engine == "fused":
-            raise ValueError(f"{what}(engine='fused'): {why}")
-        return not why
+        if why and engine != "auto":
+            raise ValueError(f"{what}(engine='{engine}'): {why}")
+        return None if why else dfw
+
+    @staticmethod
+    def _bulk_name(dfw) -> str:
+        return "wide" if dfw.__name__.endswith("dense_forward_wide") else "fused"
 
     def _bulk_rows(self, xb) -> torch.Tensor:
         """Rows for the fused kernel: an fp32 device tensor [n, D] with contiguous features."""
@@ -700,8 +709,8 @@ class Model:
     @torch.no_grad()
     def predict(self, x, batch_size: int = 32, callbacks: Optional[Sequence[Callback]] = None,
                 verbose: int = 0, engine: str = "auto") -> np.ndarray:
-        """``engine``: "auto" | "fused" | "layers" (see ``_bulk_engine``); ``last_predict_engine`` says
-        which ran.  On the fused path arrays without callbacks run in chunks of
+        """``engine``: "auto" | "fused" | "layers" | "wide" (see ``_bulk_engine``); ``last_predict_engine``
+        says which ran.  On the fused path arrays without callbacks run in chunks of
         ``max(batch_size, 1 << 20)`` rows, each chunk copied into its place in the one host array the call
         returns as soon as its launch is queued (no join on the device, no second pass on the host); with
         callbacks or a ``Stream`` every batch is a host array, as in the layer loop.  A model compiled
@@ -716,9 +725,9 @@ class Model:
         for cb in cbs:
             cb.set_model(self)
         outs = []
-        if self._bulk_engine("predict", engine, x):
-            from ..ops import dense_forward as dfw
-            self.last_predict_engine = "fused"
+        dfw = self._bulk_engine("predict", engine, x)
+        if dfw is not None:
+            self.last_predict_engine = self._bulk_name(dfw)
             if not cbs and not isinstance(x, Stream):
                 n, chunk = len(x), max(batch_size, 1 << 20)
                 host = np.empty((n, *self.output_shape), np.float32)
@@ -755,16 +764,16 @@ class Model:
             return self._fused.evaluate(x, batch_size=max(batch_size, 65536))
         xs = np.asarray(x) if not isinstance(x, torch.Tensor) else x
         ys = xs if y is None else (np.asarray(y) if not isinstance(y, torch.Tensor) else y)
-        if self._bulk_engine("evaluate", engine, xs, score=y is None, need_mse=True):
-            from ..ops import dense_forward as dfw
+        dfw = self._bulk_engine("evaluate", engine, xs, score=y is None, need_mse=True)
+        if dfw is not None:
             xd = self._bulk_rows(xs)
             yd = None if y is None else self._bulk_rows(ys)
             if yd is not None and tuple(yd.shape) != (len(xd), int(self.output_shape[-1])):
-                if engine == "fused":
-                    raise ValueError(f"evaluate(engine='fused'): y of shape {tuple(yd.shape)} is not "
+                if engine != "auto":
+                    raise ValueError(f"evaluate(engine='{engine}'): y of shape {tuple(yd.shape)} is not "
                                      f"[{len(xd)}, {int(self.output_shape[-1])}] rows")
             else:
-                self.last_evaluate_engine = "fused"
+                self.last_evaluate_engine = self._bulk_name(dfw)
                 loss, corr = dfw.evaluate_sums(self, xd, yd)
                 n = max(len(xd), 1)
                 return loss / n, corr / n
@@ -787,12 +796,11 @@ class Model:
         if len(self._input_shape()) != 1 or tuple(self.output_shape) != (D,):
             raise ValueError(f"scores need a stack with one unit per feature (input {tuple(self._input_shape())}, "
                              f"output {tuple(self.output_shape)})")
-        fused = self._bulk_engine("score", engine, x, score=True)
-        self.last_score_engine = "fused" if fused else "layers"
+        dfw = self._bulk_engine("score", engine, x, score=True)
+        fused = dfw is not None
+        self.last_score_engine = self._bulk_name(dfw) if fused else "layers"
         sc = sh = None
-        if fused:
-            from ..ops import dense_forward as dfw
-        else:
+        if not fused:
             from ..ops.serve import _resolve_normalizer
             sc, sh = _resolve_normalizer(normalizer, D, self, "the model has")
             if sc is not None:
