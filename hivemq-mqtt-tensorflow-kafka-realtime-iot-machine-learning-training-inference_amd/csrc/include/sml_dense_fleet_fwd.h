@@ -2,7 +2,8 @@
 // shape, each over its own slice of one flat row array, in one launch.  Its LDS plan, the check that
 // names the limit a launch exceeds and the walk over (workgroup, model) segments.  Plain C++17 with no
 // HIP header, in the manner of sml_dense_fwd_plan.h, whose limits, layer table and image layout hold
-// here unchanged; ops/dense_fleet_forward.py mirrors the plan and the check.
+// here unchanged; ops/dense_fleet_forward.py mirrors the plan and the check (csrc/tests/dense_fwd_check.cpp
+// asks both on the host).
 //
 // PAIR SPACE.  A tile pair is 32 rows, aligned to its model's first row, so no tile holds rows of two
 // models.  pair_base[M + 1] is the prefix sum of ceil(rows / 32); G = pair_base[M].  Workgroup b of

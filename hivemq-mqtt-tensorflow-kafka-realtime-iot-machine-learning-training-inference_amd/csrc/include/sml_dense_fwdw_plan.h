@@ -1,8 +1,9 @@
 // The fused bulk forward of WIDE Dense stacks (kernels/dense_forward_wide.hip): its limits, its layer
 // table, the offsets of the packed bf16 weight image, its LDS plan and the check that names the limit a
-// stack exceeds.  Plain C++17 with no HIP header, in the manner of sml_dense_fwd_plan.h.
-// ops/dense_forward_wide.py mirrors the check and the plan in Python, because supports() must answer
-// without a built extension.
+// stack exceeds.  Plain C++17 with no HIP header, over sml_dense_fwd_plan.h: the layer table (DenseFwdLayer,
+// offsets in words here), DFW_MAXLAYERS, DFW_ACT_LAST and the shared rules of the check are that header's.
+// ops/dense_forward_wide.py mirrors the plan in Python (the check is ops/dense_forward.py's), because
+// supports() must answer without a built extension.
 //
 // IMAGE (16-bit words; offsets in words).  Per layer, blocks of 32 inputs (kb) by 16 units (ub) in the
 // order of a v_mfma_f32_16x16x32_bf16 A fragment:
@@ -15,10 +16,12 @@
 #include <cstdint>
 #include <string>
 
+#include "sml_dense_fwd_plan.h"
+
 namespace sml {
 
 enum : int {
-  DFWW_MAXLAYERS = 8,
+  DFWW_MAXLAYERS = DFW_MAXLAYERS,
   DFWW_MAXW = 512,             // units / inputs of a layer
   DFWW_WAVES = 8,              // waves of a workgroup; wave w owns the unit blocks w, w + 8, w + 16, w + 24
   DFWW_MAXUB = 4,              // unit blocks a wave owns at most: DFWW_MAXW / 16 / DFWW_WAVES
@@ -27,16 +30,9 @@ enum : int {
   DFWW_ROW_PAD = 8,            // words added to an activation row in LDS (16-byte aligned, off the bank stride)
   DFWW_PART_WORDS = 5,         // a wave's epilogue partial of a row: squared error, (max, argmax) of y and of the target
   DFWW_LDS_BYTES = 160 * 1024,
-  DFWW_STATIC_LDS = 2048,      // the kernel's own static LDS
-  DFWW_ACT_LAST = 3            // activation codes 0 .. 3 (Act of sml_common.h: ACT_LINEAR .. ACT_SIGMOID)
+  DFWW_STATIC_LDS = 2048       // the kernel's own static LDS
 };
 static_assert(DFWW_MAXUB * DFWW_WAVES * 16 == DFWW_MAXW, "a wave's accumulators hold its whole unit slice");
-
-struct DenseFwdWLayer {
-  int in, out;
-  int act;             // ACT_* code
-  int w_off, b_off;    // word offsets of the layer's blocks and of its padded fp32 bias in the image
-};
 
 struct DenseFwdWPlan {
   int img_words;
@@ -49,16 +45,7 @@ constexpr int dfww_pad16(int n) { return (n + 15) / 16 * 16; }
 constexpr int dfww_pad32(int n) { return (n + 31) / 32 * 32; }
 
 // fills w_off / b_off from in / out; returns the words of the image
-inline int dense_fwdw_image_offsets(DenseFwdWLayer* L, int nl) {
-  int off = 0;
-  for (int l = 0; l < nl; ++l) {
-    L[l].w_off = off;
-    off += dfww_pad32(L[l].in) * dfww_pad16(L[l].out);
-    L[l].b_off = off;
-    off += 2 * dfww_pad16(L[l].out);
-  }
-  return off;
-}
+inline int dense_fwdw_image_offsets(DenseFwdLayer* L, int nl) { return dense_fwd_offsets(L, nl, 32, 2); }
 
 // tile == 0: the kernel's own choice of the rows of a tile for n rows on `cus` CUs.  One workgroup
 // runs per CU either way (153 / 229 VGPRs); the large tile fetches each weight fragment half as often
@@ -68,7 +55,7 @@ inline int dense_fwdw_rows(int64_t n, int cus, int tile) {
   return n >= (int64_t)DFWW_ROWS_LARGE * cus ? DFWW_ROWS_LARGE : DFWW_ROWS_SMALL;
 }
 
-inline DenseFwdWPlan dense_fwdw_plan(const DenseFwdWLayer* L, int nl, int rows) {
+inline DenseFwdWPlan dense_fwdw_plan(const DenseFwdLayer* L, int nl, int rows) {
   DenseFwdWPlan P{};
   int kmax = 0, off = 0;
   for (int l = 0; l < nl; ++l) {
@@ -89,35 +76,9 @@ static_assert(DFWW_ROWS_LARGE * (DFWW_MAXW + DFWW_ROW_PAD) * 2 + DFWW_STATIC_LDS
 // empty if the kernel takes the stack (D inputs, nl layers whose image offsets lie inside img_words
 // words, or anywhere if that is negative; score: the target is the input row, so out == D), else the
 // limit it exceeds
-inline std::string dense_fwdw_check(const DenseFwdWLayer* L, int nl, int D, int64_t img_words, bool score) {
-  using std::to_string;
-  if (nl < 1 || nl > DFWW_MAXLAYERS)
-    return to_string(nl) + " Dense layers: the wide fused forward takes 1.." + to_string(DFWW_MAXLAYERS) + " (MAX_LAYERS)";
-  if (D < 1 || D > DFWW_MAXW)
-    return "input width " + to_string(D) + " is outside 1.." + to_string(DFWW_MAXW) + " (MAX_WIDTH)";
-  int prev = D;
-  for (int l = 0; l < nl; ++l) {
-    if (L[l].in != prev) return "layer " + to_string(l) + " does not take the previous layer's width";
-    if (L[l].out < 1 || L[l].out > DFWW_MAXW)
-      return "layer " + to_string(l) + " has " + to_string(L[l].out) + " units: the limit is " + to_string(DFWW_MAXW) +
-             " (MAX_WIDTH)";
-    if (L[l].act < 0 || L[l].act > DFWW_ACT_LAST) return "layer " + to_string(l) + ": unknown activation";
-    prev = L[l].out;
-  }
-  if (score && prev != D)
-    return "scores against the input row need as many output units as inputs (" + to_string(prev) + " units, " +
-           to_string(D) + " inputs)";
-  if (img_words >= 0) {
-    DenseFwdWLayer T[DFWW_MAXLAYERS];
-    for (int l = 0; l < nl; ++l) T[l] = L[l];
-    const int want = dense_fwdw_image_offsets(T, nl);
-    if (img_words != want)
-      return "an image of " + to_string(img_words) + " words: the stack packs into " + to_string(want);
-    for (int l = 0; l < nl; ++l)
-      if (L[l].w_off != T[l].w_off || L[l].b_off != T[l].b_off)
-        return "layer " + to_string(l) + ": image offsets are not those of the packed layout";
-  }
-  return "";
+inline std::string dense_fwdw_check(const DenseFwdLayer* L, int nl, int D, int64_t img_words, bool score) {
+  const std::string why = dense_fwd_check_rows(L, nl, D, score, DFWW_MAXW, "wide fused");
+  return why.empty() ? dense_fwd_check_image(L, nl, img_words, 32, 2, "words") : why;
 }
 
 }  // namespace sml

@@ -536,8 +536,8 @@ hipError_t dense_fleet_fwd_launch(const DenseFleetFwdArgs& args, hipStream_t str
 // The outputs of dense_fwd_launch with the rounding points of the bf16 trainers' forward: every
 // contraction is bf16(h) . bf16(W) on v_mfma_f32_16x16x32_bf16 with fp32 accumulation, bias, activation,
 // scores and sums in fp32 / double.  Weights stream from a bf16 image in device memory (L2), a tile's
-// activations stay in LDS.  The limits, DenseFwdWLayer, the image layout, the LDS plan and
-// dense_fwdw_check are in sml_dense_fwdw_plan.h (plain C++).
+// activations stay in LDS.  The limits, the image layout (the table's offsets are in words), the LDS plan
+// and dense_fwdw_check are in sml_dense_fwdw_plan.h (plain C++).
 struct DenseFwdWArgs {
   const float* x;          // [n, D] rows, features contiguous
   int64_t ldx;
@@ -556,10 +556,10 @@ struct DenseFwdWArgs {
   int nl, D;
   int max_blocks;          // 0: as many workgroups as the CUs hold
   int tile;                // rows of a workgroup's tile: 64, 128 or 0 (the kernel's choice)
-  DenseFwdWLayer L[DFWW_MAXLAYERS];
+  DenseFwdLayer L[DFW_MAXLAYERS];
 };
 // workgroups dense_fwdw_launch starts for n >= 1 rows of a stack that passes dense_fwdw_check
-int dense_fwdw_grid(const DenseFwdWLayer* L, int nl, int64_t n, int max_blocks, int tile);
+int dense_fwdw_grid(const DenseFwdLayer* L, int nl, int64_t n, int max_blocks, int tile);
 hipError_t dense_fwdw_launch(const DenseFwdWArgs& args, hipStream_t stream);
 
 // ---- fused MSE + categorical accuracy (loss.hip) ----

@@ -50,10 +50,9 @@
 // v_pk_fma_f32 that sit between MFMAs, where the packed form issues slower than the two scalar ones
 // (_build.py's note on no-slp); without it there are none, at the same 113 / 182 / 296 VGPRs.  The
 // feature switch is used rather than no-slp because it holds for every pass, not the SLP vectoriser alone.
-#include <atomic>
-
 #include "sml_common.h"
 #include "sml_dense_fwd_dev.h"
+#include "sml_dense_fwd_launch.h"
 #include "sml_ops.h"
 
 namespace sml {
@@ -130,45 +129,10 @@ __global__ __launch_bounds__(MB == 8 ? 256 : 512) void dense_fwd_kernel(DenseFwd
 std::string args_check(const DenseFwdArgs& a) {
   if (a.nl < 1 || a.nl > DFW_MAXLAYERS) return dense_fwd_check(a.L, a.nl, a.D, -1, false);
   const std::string why = dense_fwd_check(a.L, a.nl, a.D, a.img_floats, a.score != nullptr || (a.sums && !a.y));
-  if (!why.empty()) return why;
-  if (!a.x || !a.image || ((uintptr_t)a.image & 15) || a.n < 1 || a.ldx < a.D) return "bad rows or image";
-  if ((a.scale == nullptr) != (a.shift == nullptr)) return "scale and shift come together";
-  if (a.flag && !a.score) return "flags need scores";
-  if (a.y && (!a.sums || a.score || a.ldy < a.L[a.nl - 1].out)) return "own targets are for sums alone";
-  if (!a.rec && !a.score && !a.sums) return "nothing to compute";
-  if (a.max_blocks < 0) return "max_blocks is negative";
-  return "";
+  return why.empty() ? dense_fwd_args_why(a, a.image, a.sums) : why;
 }
 
-constexpr int MAXDEV = 64;
-
-int cur_device() {
-  int dev = 0;
-  return hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < MAXDEV ? dev : -1;
-}
-
-// CUs of the current device, asked once per device
-int cu_count() {
-  static std::atomic<int> cus[MAXDEV];
-  const int dev = cur_device();
-  int n = dev >= 0 ? cus[dev].load(std::memory_order_relaxed) : 0;
-  if (n < 1) {
-    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev < 0 ? 0 : dev) != hipSuccess || n < 1) n = 256;
-    if (dev >= 0) cus[dev].store(n, std::memory_order_relaxed);
-  }
-  return n;
-}
-
-// hipFuncAttributeMaxDynamicSharedMemorySize only grows: set once per device and instance for the
-// largest plan seen
-hipError_t ensure_lds(const void* fn, int instance, int bytes) {
-  static std::atomic<int> have[MAXDEV][3];
-  const int dev = cur_device();
-  if (dev >= 0 && have[dev][instance].load(std::memory_order_relaxed) >= bytes) return hipSuccess;
-  const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-  if (e == hipSuccess && dev >= 0) have[dev][instance].store(bytes, std::memory_order_relaxed);
-  return e;
-}
+DenseFwdLdsMark<3> lds_mark;   // of dense_fwd_kernel<2 / 4 / 8>
 
 }  // namespace
 
@@ -176,7 +140,7 @@ int dense_fwd_grid(const DenseFwdLayer* L, int nl, int D, int64_t n, int max_blo
   const DenseFwdPlan P = dense_fwd_plan(L, nl, D);
   const int64_t pairs = ((n + 15) / 16 + 1) / 2;
   const int64_t want = (pairs + P.waves - 1) / P.waves;   // a pair per wave at least
-  const int64_t cap = max_blocks > 0 ? max_blocks : cu_count();
+  const int64_t cap = max_blocks > 0 ? max_blocks : dense_fwd_cu_count();
   return (int)(want < cap ? want : cap);
 }
 
@@ -187,7 +151,7 @@ hipError_t dense_fwd_launch(const DenseFwdArgs& a, hipStream_t stream) {
   const void* fn = P.mb == 2   ? reinterpret_cast<const void*>(dense_fwd_kernel<2>)
                    : P.mb == 4 ? reinterpret_cast<const void*>(dense_fwd_kernel<4>)
                                : reinterpret_cast<const void*>(dense_fwd_kernel<8>);
-  const hipError_t e = ensure_lds(fn, P.mb == 2 ? 0 : P.mb == 4 ? 1 : 2, P.lds_bytes);
+  const hipError_t e = lds_mark.ensure(fn, P.mb == 2 ? 0 : P.mb == 4 ? 1 : 2, P.lds_bytes);
   if (e != hipSuccess) return e;
   const dim3 block(64 * P.waves);
   if (P.mb == 2) hipLaunchKernelGGL(dense_fwd_kernel<2>, dim3(grid), block, (size_t)P.lds_bytes, stream, a, P);

@@ -30,10 +30,9 @@
 // the segment's barrier; the host folds the slots in slot order.
 //
 // Three instances by padded width, as dense_forward.hip; built without packed fp32 like it.
-#include <atomic>
-
 #include "sml_common.h"
 #include "sml_dense_fwd_dev.h"
+#include "sml_dense_fwd_launch.h"
 #include "sml_ops.h"
 
 namespace sml {
@@ -172,46 +171,26 @@ __global__ __launch_bounds__(MB == 8 ? 256 : 512) void dense_fwd_fleet_kernel(De
   }
 }
 
-constexpr int MAXDEV = 64;
-
-int cur_device() {
-  int dev = 0;
-  return hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < MAXDEV ? dev : -1;
-}
-
-// CUs of the current device, asked once per device
-int cu_count() {
-  static std::atomic<int> cus[MAXDEV];
-  const int dev = cur_device();
-  int n = dev >= 0 ? cus[dev].load(std::memory_order_relaxed) : 0;
-  if (n < 1) {
-    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev < 0 ? 0 : dev) != hipSuccess || n < 1) n = 256;
-    if (dev >= 0) cus[dev].store(n, std::memory_order_relaxed);
-  }
-  return n;
-}
-
 // what the launcher can check without reading device memory; the binding checks the table's host copy
 bool args_ok(const DenseFleetFwdArgs& a) {
   if (a.nl < 1 || a.nl > DFW_MAXLAYERS) return false;
   const bool scored = a.score != nullptr || (a.slot_sums && !a.y);
   if (!dense_fleet_fwd_check(a.L, a.nl, a.D, a.img_floats, scored, a.M, nullptr, a.n, a.stride).empty()) return false;
-  if (!a.x || !a.images || ((uintptr_t)a.images & 15) || !a.table || !a.pair_base || a.n < 1 || a.ldx < a.D) return false;
+  if (*dense_fwd_args_why(a, a.images, a.slot_sums)) return false;
+  if (!a.table || !a.pair_base) return false;
   if (a.pairs < 1 || a.pairs > (a.n + DFF_PAIR_ROWS - 1) / DFF_PAIR_ROWS + a.M) return false;
-  if ((a.scale == nullptr) != (a.shift == nullptr)) return false;
-  if (a.flag && (!a.score || !a.thr)) return false;
-  if (a.slot_sums && !a.slot_model) return false;
-  if (a.y && (!a.slot_sums || a.score || a.ldy < a.L[a.nl - 1].out)) return false;
-  if (!a.rec && !a.score && !a.slot_sums) return false;
-  return a.max_blocks >= 0;
+  if (a.flag && !a.thr) return false;
+  return !a.slot_sums || a.slot_model;
 }
+
+DenseFwdLdsMark<3> lds_mark;   // of dense_fwd_fleet_kernel<2 / 4 / 8>
 
 }  // namespace
 
 int dense_fleet_fwd_grid(const DenseFwdLayer* L, int nl, int D, int64_t pairs, int max_blocks) {
   const DenseFleetFwdPlan F = dense_fleet_fwd_plan(L, nl, D);
   const int64_t want = (pairs + F.waves - 1) / F.waves;   // a pair per wave at least
-  const int64_t cap = max_blocks > 0 ? max_blocks : cu_count();
+  const int64_t cap = max_blocks > 0 ? max_blocks : dense_fwd_cu_count();
   return (int)(want < cap ? want : cap);
 }
 
@@ -223,15 +202,8 @@ hipError_t dense_fleet_fwd_launch(const DenseFleetFwdArgs& a, hipStream_t stream
   const void* fn = mb == 2   ? reinterpret_cast<const void*>(dense_fwd_fleet_kernel<2>)
                    : mb == 4 ? reinterpret_cast<const void*>(dense_fwd_fleet_kernel<4>)
                              : reinterpret_cast<const void*>(dense_fwd_fleet_kernel<8>);
-  // hipFuncAttributeMaxDynamicSharedMemorySize only grows: set once per device and instance for the
-  // largest plan seen
-  static std::atomic<int> have[MAXDEV][3];
-  const int dev = cur_device();
-  if (dev < 0 || have[dev][inst].load(std::memory_order_relaxed) < F.one.lds_bytes) {
-    const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, F.one.lds_bytes);
-    if (e != hipSuccess) return e;
-    if (dev >= 0) have[dev][inst].store(F.one.lds_bytes, std::memory_order_relaxed);
-  }
+  const hipError_t e = lds_mark.ensure(fn, inst, F.one.lds_bytes);
+  if (e != hipSuccess) return e;
   const dim3 block(64 * F.waves);
   const size_t lds = (size_t)F.one.lds_bytes;
   if (mb == 2) hipLaunchKernelGGL(dense_fwd_fleet_kernel<2>, dim3(grid), block, lds, stream, a, F);

@@ -42,16 +42,16 @@
 //
 // A ROW'S BITS depend on the row and the weights only: the k order of a unit is kb ascending whatever
 // RT, the grid or the row's place in the tile, and the fold over lanes and waves is fixed.
-#include <atomic>
 #include <climits>
 
 #include "sml_common.h"
+#include "sml_dense_fwd_launch.h"
 #include "sml_ops.h"
 
 namespace sml {
 namespace {
 
-static_assert(ACT_LINEAR == 0 && DFWW_ACT_LAST == ACT_SIGMOID, "the check's activation range is Act's");
+static_assert(ACT_LINEAR == 0 && DFW_ACT_LAST == ACT_SIGMOID, "the check's activation range is Act's");
 constexpr int NWV = DFWW_WAVES, NTHR = 64 * DFWW_WAVES;
 
 __device__ __forceinline__ f32x4 mfma_k32(s16x8 a, s16x8 b, f32x4 c) {
@@ -288,53 +288,20 @@ __global__ __launch_bounds__(NTHR) void dense_fwdw_kernel(DenseFwdWArgs a, int S
 }
 
 std::string args_check(const DenseFwdWArgs& a) {
-  if (a.nl < 1 || a.nl > DFWW_MAXLAYERS) return dense_fwdw_check(a.L, a.nl, a.D, -1, false);
-  const std::string why = dense_fwdw_check(a.L, a.nl, a.D, a.img_words, a.score != nullptr || (a.sums && !a.y));
+  if (a.nl < 1 || a.nl > DFW_MAXLAYERS) return dense_fwdw_check(a.L, a.nl, a.D, -1, false);
+  std::string why = dense_fwdw_check(a.L, a.nl, a.D, a.img_words, a.score != nullptr || (a.sums && !a.y));
+  if (why.empty()) why = dense_fwd_args_why(a, a.image, a.sums);
   if (!why.empty()) return why;
-  if (!a.x || !a.image || ((uintptr_t)a.image & 15) || a.n < 1 || a.ldx < a.D) return "bad rows or image";
-  if ((a.scale == nullptr) != (a.shift == nullptr)) return "scale and shift come together";
-  if (a.flag && !a.score) return "flags need scores";
-  if (a.y && (!a.sums || a.score || a.ldy < a.L[a.nl - 1].out)) return "own targets are for sums alone";
-  if (!a.rec && !a.score && !a.sums) return "nothing to compute";
-  if (a.max_blocks < 0) return "max_blocks is negative";
   if (a.tile != 0 && a.tile != DFWW_ROWS_SMALL && a.tile != DFWW_ROWS_LARGE) return "a tile has 64 or 128 rows";
   return "";
 }
 
-constexpr int MAXDEV = 64;
-
-int cur_device() {
-  int dev = 0;
-  return hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < MAXDEV ? dev : -1;
-}
-
-// CUs of the current device, asked once per device
-int cu_count() {
-  static std::atomic<int> cus[MAXDEV];
-  const int dev = cur_device();
-  int n = dev >= 0 ? cus[dev].load(std::memory_order_relaxed) : 0;
-  if (n < 1) {
-    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev < 0 ? 0 : dev) != hipSuccess || n < 1) n = 256;
-    if (dev >= 0) cus[dev].store(n, std::memory_order_relaxed);
-  }
-  return n;
-}
-
-// hipFuncAttributeMaxDynamicSharedMemorySize only grows: set once per device and instance for the
-// largest plan seen
-hipError_t ensure_lds(const void* fn, int instance, int bytes) {
-  static std::atomic<int> have[MAXDEV][2];
-  const int dev = cur_device();
-  if (dev >= 0 && have[dev][instance].load(std::memory_order_relaxed) >= bytes) return hipSuccess;
-  const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-  if (e == hipSuccess && dev >= 0) have[dev][instance].store(bytes, std::memory_order_relaxed);
-  return e;
-}
+DenseFwdLdsMark<2> lds_mark;   // of dense_fwdw_kernel<4 / 8>
 
 }  // namespace
 
-int dense_fwdw_grid(const DenseFwdWLayer* L, int nl, int64_t n, int max_blocks, int tile) {
-  const int cus = cu_count();
+int dense_fwdw_grid(const DenseFwdLayer* L, int nl, int64_t n, int max_blocks, int tile) {
+  const int cus = dense_fwd_cu_count();
   const DenseFwdWPlan P = dense_fwdw_plan(L, nl, dense_fwdw_rows(n, cus, tile));
   const int64_t tiles = (n + P.rows - 1) / P.rows;
   const int64_t cap = max_blocks > 0 ? max_blocks : cus;
@@ -343,11 +310,11 @@ int dense_fwdw_grid(const DenseFwdWLayer* L, int nl, int64_t n, int max_blocks, 
 
 hipError_t dense_fwdw_launch(const DenseFwdWArgs& a, hipStream_t stream) {
   if (!args_check(a).empty()) return hipErrorInvalidValue;
-  const DenseFwdWPlan P = dense_fwdw_plan(a.L, a.nl, dense_fwdw_rows(a.n, cu_count(), a.tile));
+  const DenseFwdWPlan P = dense_fwdw_plan(a.L, a.nl, dense_fwdw_rows(a.n, dense_fwd_cu_count(), a.tile));
   const int grid = dense_fwdw_grid(a.L, a.nl, a.n, a.max_blocks, a.tile);
   const bool large = P.rows == DFWW_ROWS_LARGE;
   const void* fn = large ? reinterpret_cast<const void*>(dense_fwdw_kernel<8>) : reinterpret_cast<const void*>(dense_fwdw_kernel<4>);
-  const hipError_t e = ensure_lds(fn, large ? 1 : 0, P.lds_bytes);
+  const hipError_t e = lds_mark.ensure(fn, large ? 1 : 0, P.lds_bytes);
   if (e != hipSuccess) return e;
   if (large) hipLaunchKernelGGL(dense_fwdw_kernel<8>, dim3(grid), dim3(NTHR), (size_t)P.lds_bytes, stream, a, P.stride);
   else hipLaunchKernelGGL(dense_fwdw_kernel<4>, dim3(grid), dim3(NTHR), (size_t)P.lds_bytes, stream, a, P.stride);

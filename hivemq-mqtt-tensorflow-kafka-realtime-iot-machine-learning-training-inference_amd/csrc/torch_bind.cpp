@@ -1142,7 +1142,8 @@ std::string dense_mb_check(const std::vector<std::vector<double>>& table, int64_
                              own_targets, (int)std::min<int64_t>(std::max<int64_t>(precision, -1), 2));
 }
 
-// Table rows of the fused bulk forward: (in, units, act, w_off, b_off), offsets in floats of the image.
+// Table rows of the fused bulk forwards: (in, units, act, w_off, b_off), offsets in floats of the image
+// (16-bit words of the wide variant's).
 static int dense_fwd_table(const std::vector<std::vector<int64_t>>& table, sml::DenseFwdLayer* L) {
   if (table.size() > (size_t)sml::DFW_MAXLAYERS) return (int)table.size();
   int nl = 0;
@@ -1161,27 +1162,21 @@ std::string dense_fwd_check(const std::vector<std::vector<int64_t>>& table, int6
   return sml::dense_fwd_check(L, nl, nl ? L[0].in : 0, img_floats, score);
 }
 
-// The whole stack over the rows of x in one launch (dense_forward.hip).  rec [n, out], score [n] and
-// flag [n] (uint8) are written where given; sums returns the per-workgroup partials [grid, 2] (float64:
-// sum of per-row mean squared errors, rows whose argmax matches) against y [n, out] or, without y, the
-// normalised row.
-c10::optional<at::Tensor> dense_forward(const at::Tensor& x, const at::Tensor& image,
-                                        const std::vector<std::vector<int64_t>>& table,
-                                        const c10::optional<at::Tensor>& scale, const c10::optional<at::Tensor>& shift,
-                                        const c10::optional<at::Tensor>& rec, const c10::optional<at::Tensor>& score,
-                                        const c10::optional<at::Tensor>& flag, double threshold, bool sums,
-                                        const c10::optional<at::Tensor>& y, int64_t max_blocks) {
-  check_dev(x, "x", at::kFloat);
-  check_dev(image, "image", at::kFloat);
-  TORCH_CHECK(image.dim() == 1 && image.is_contiguous(), "image must be a flat fp32 tensor");
-  for (const c10::optional<at::Tensor>* t : {&scale, &shift, &rec, &score, &flag, &y})
-    TORCH_CHECK(!t->has_value() || (*t)->device() == x.device(), "every tensor must live on x's device");
-  TORCH_CHECK(image.device() == x.device(), "image must live on x's device");
-  sml::DenseFwdArgs a{};
-  const bool scored = score.has_value() || (sums && !y.has_value());
-  const std::string why = dense_fwd_check(table, image.numel(), scored);
-  TORCH_CHECK(why.empty(), "dense_forward: ", why);
-  a.nl = dense_fwd_table(table, a.L);
+// What the three fused-forward bindings share.  a.L / a.nl hold the table and `why` is the variant's check
+// of it; after that check this fills D, x, ldx, n, scale, shift, rec, score, flag, y, ldy and max_blocks
+// of the variant's args struct by name and checks each tensor against n rows and the stack's widths.
+// flag_ok / flag_needs: what flags need besides their own shape (the fleet adds thresholds); `more`: a
+// further optional tensor that must live on x's device.
+template <class A>
+static void dense_fwd_io(A& a, const char* who, const std::string& why, const at::Tensor& x,
+                         const c10::optional<at::Tensor>& scale, const c10::optional<at::Tensor>& shift,
+                         const c10::optional<at::Tensor>& rec, const c10::optional<at::Tensor>& score,
+                         const c10::optional<at::Tensor>& flag, bool flag_ok, const char* flag_needs, bool sums,
+                         const c10::optional<at::Tensor>& y, int64_t max_blocks,
+                         const c10::optional<at::Tensor>* more = nullptr) {
+  for (const c10::optional<at::Tensor>* t : {&scale, &shift, &rec, &score, &flag, &y, more})
+    TORCH_CHECK(!t || !t->has_value() || (*t)->device() == x.device(), "every tensor must live on x's device");
+  TORCH_CHECK(why.empty(), who, ": ", why);
   a.D = a.L[0].in;
   const int64_t O = a.L[a.nl - 1].out, n = x.dim() == 2 ? x.size(0) : 0;
   TORCH_CHECK(x.dim() == 2 && n >= 1 && x.size(1) == a.D && (a.D == 1 || x.stride(1) == 1) &&
@@ -1190,9 +1185,7 @@ c10::optional<at::Tensor> dense_forward(const at::Tensor& x, const at::Tensor& i
   a.x = x.data_ptr<float>();
   a.ldx = n == 1 ? a.D : x.stride(0);
   a.n = n;
-  a.image = image.data_ptr<float>();
-  a.img_floats = (int)image.numel();
-  TORCH_CHECK(scale.has_value() == shift.has_value(), "scale and shift come together");
+  TORCH_CHECK(scale.has_value() == shift.has_value(), sml::DFW_WHY_PAIRED);
   if (scale.has_value()) {
     check_dev(*scale, "scale", at::kFloat);
     check_dev(*shift, "shift", at::kFloat);
@@ -1213,23 +1206,47 @@ c10::optional<at::Tensor> dense_forward(const at::Tensor& x, const at::Tensor& i
     a.score = score->data_ptr<float>();
   }
   if (flag.has_value()) {
-    TORCH_CHECK(score.has_value(), "flags need scores");
+    TORCH_CHECK(flag_ok, flag_needs);
     TORCH_CHECK(flag->is_cuda() && (flag->scalar_type() == at::kByte || flag->scalar_type() == at::kBool) && flag->dim() == 1 &&
                     flag->numel() == n && flag->is_contiguous(), "flag must be a contiguous device uint8 / bool [n]");
     a.flag = static_cast<uint8_t*>(flag->data_ptr());
   }
-  a.threshold = (float)threshold;
   if (y.has_value()) {
     check_dev(*y, "y", at::kFloat);
-    TORCH_CHECK(sums && !score.has_value(), "own targets are for sums alone");
+    TORCH_CHECK(sums && !score.has_value(), sml::DFW_WHY_OWN_TARGETS);
     TORCH_CHECK(y->dim() == 2 && y->size(0) == n && y->size(1) == O && (O == 1 || y->stride(1) == 1) &&
                     (n == 1 || y->stride(0) >= O), "y must be [n, ", O, "] rows with contiguous features");
     a.y = y->data_ptr<float>();
     a.ldy = n == 1 ? O : y->stride(0);
   }
-  TORCH_CHECK(rec.has_value() || score.has_value() || sums, "nothing to compute");
+  TORCH_CHECK(rec.has_value() || score.has_value() || sums, sml::DFW_WHY_NOTHING);
   TORCH_CHECK(max_blocks >= 0 && max_blocks < (1 << 20), "bad max_blocks");
   a.max_blocks = (int)max_blocks;
+}
+
+// The whole stack over the rows of x in one launch (dense_forward.hip).  rec [n, out], score [n] and
+// flag [n] (uint8) are written where given; sums returns the per-workgroup partials [grid, 2] (float64:
+// sum of per-row mean squared errors, rows whose argmax matches) against y [n, out] or, without y, the
+// normalised row.
+c10::optional<at::Tensor> dense_forward(const at::Tensor& x, const at::Tensor& image,
+                                        const std::vector<std::vector<int64_t>>& table,
+                                        const c10::optional<at::Tensor>& scale, const c10::optional<at::Tensor>& shift,
+                                        const c10::optional<at::Tensor>& rec, const c10::optional<at::Tensor>& score,
+                                        const c10::optional<at::Tensor>& flag, double threshold, bool sums,
+                                        const c10::optional<at::Tensor>& y, int64_t max_blocks) {
+  check_dev(x, "x", at::kFloat);
+  check_dev(image, "image", at::kFloat);
+  TORCH_CHECK(image.dim() == 1 && image.is_contiguous(), "image must be a flat fp32 tensor");
+  TORCH_CHECK(image.device() == x.device(), "image must live on x's device");
+  sml::DenseFwdArgs a{};
+  const bool scored = score.has_value() || (sums && !y.has_value());
+  a.nl = dense_fwd_table(table, a.L);
+  dense_fwd_io(a, "dense_forward", sml::dense_fwd_check(a.L, a.nl, a.nl ? a.L[0].in : 0, image.numel(), scored), x, scale,
+               shift, rec, score, flag, score.has_value(), sml::DFW_WHY_FLAGS, sums, y, max_blocks);
+  const int64_t n = a.n;
+  a.image = image.data_ptr<float>();
+  a.img_floats = (int)image.numel();
+  a.threshold = (float)threshold;
   c10::hip::HIPGuard guard(x.device().index());
   c10::optional<at::Tensor> part;
   if (sums) {
@@ -1241,22 +1258,10 @@ c10::optional<at::Tensor> dense_forward(const at::Tensor& x, const at::Tensor& i
 }
 
 // ---- the wide variant (dense_forward_wide.hip, sml_dense_fwdw_plan.h) ----
-// Table rows: (in, units, act, w_off, b_off), offsets in 16-bit words of the bf16 image.
-static int dense_fwdw_table(const std::vector<std::vector<int64_t>>& table, sml::DenseFwdWLayer* L) {
-  if (table.size() > (size_t)sml::DFWW_MAXLAYERS) return (int)table.size();
-  int nl = 0;
-  for (const auto& t : table) {
-    TORCH_CHECK(t.size() == 5, "layer descriptor: (in, units, act, w_off, b_off)");
-    auto i32 = [](int64_t v) { return (int)std::min<int64_t>(std::max<int64_t>(v, -1), 1 << 30); };
-    L[nl++] = sml::DenseFwdWLayer{i32(t[0]), i32(t[1]), i32(t[2]), i32(t[3]), i32(t[4])};
-  }
-  return nl;
-}
-
-// Empty when dense_forward_wide.hip takes the stack (score: against the input row), else the limit it exceeds.
+// Table rows as dense_fwd_table reads them, with offsets in 16-bit words of the bf16 image.  Empty when dense_forward_wide.hip takes the stack (score: against the input row), else the limit it exceeds.
 std::string dense_fwdw_check(const std::vector<std::vector<int64_t>>& table, int64_t img_words, bool score) {
-  sml::DenseFwdWLayer L[sml::DFWW_MAXLAYERS] = {};
-  const int nl = dense_fwdw_table(table, L);
+  sml::DenseFwdLayer L[sml::DFW_MAXLAYERS] = {};
+  const int nl = dense_fwd_table(table, L);
   return sml::dense_fwdw_check(L, nl, nl ? L[0].in : 0, img_words, score);
 }
 
@@ -1271,63 +1276,17 @@ c10::optional<at::Tensor> dense_forward_wide(const at::Tensor& x, const at::Tens
   check_dev(x, "x", at::kFloat);
   check_dev(image, "image", at::kShort);
   TORCH_CHECK(image.dim() == 1 && image.is_contiguous(), "image must be a flat int16 tensor");
-  for (const c10::optional<at::Tensor>* t : {&scale, &shift, &rec, &score, &flag, &y})
-    TORCH_CHECK(!t->has_value() || (*t)->device() == x.device(), "every tensor must live on x's device");
   TORCH_CHECK(image.device() == x.device(), "image must live on x's device");
   sml::DenseFwdWArgs a{};
   const bool scored = score.has_value() || (sums && !y.has_value());
-  const std::string why = dense_fwdw_check(table, image.numel(), scored);
-  TORCH_CHECK(why.empty(), "dense_forward_wide: ", why);
-  a.nl = dense_fwdw_table(table, a.L);
-  a.D = a.L[0].in;
-  const int64_t O = a.L[a.nl - 1].out, n = x.dim() == 2 ? x.size(0) : 0;
-  TORCH_CHECK(x.dim() == 2 && n >= 1 && x.size(1) == a.D && (a.D == 1 || x.stride(1) == 1) &&
-                  (n == 1 || x.stride(0) >= a.D),
-              "x must be [n >= 1, ", a.D, "] rows with contiguous features");
-  a.x = x.data_ptr<float>();
-  a.ldx = n == 1 ? a.D : x.stride(0);
-  a.n = n;
+  a.nl = dense_fwd_table(table, a.L);
+  dense_fwd_io(a, "dense_forward_wide", sml::dense_fwdw_check(a.L, a.nl, a.nl ? a.L[0].in : 0, image.numel(), scored), x,
+               scale, shift, rec, score, flag, score.has_value(), sml::DFW_WHY_FLAGS, sums, y, max_blocks);
+  TORCH_CHECK(tile == 0 || tile == sml::DFWW_ROWS_SMALL || tile == sml::DFWW_ROWS_LARGE, "tile must be 0, 64 or 128");
+  const int64_t n = a.n;
   a.image = reinterpret_cast<const uint16_t*>(image.data_ptr<int16_t>());
   a.img_words = (int)image.numel();
-  TORCH_CHECK(scale.has_value() == shift.has_value(), "scale and shift come together");
-  if (scale.has_value()) {
-    check_dev(*scale, "scale", at::kFloat);
-    check_dev(*shift, "shift", at::kFloat);
-    TORCH_CHECK(scale->numel() == a.D && shift->numel() == a.D && scale->is_contiguous() && shift->is_contiguous(),
-                "scale / shift must have ", a.D, " entries");
-    a.scale = scale->data_ptr<float>();
-    a.shift = shift->data_ptr<float>();
-  }
-  if (rec.has_value()) {
-    check_dev(*rec, "rec", at::kFloat);
-    TORCH_CHECK(rec->dim() == 2 && rec->size(0) == n && rec->size(1) == O && rec->is_contiguous(), "rec must be a contiguous [n, ",
-                O, "]");
-    a.rec = rec->data_ptr<float>();
-  }
-  if (score.has_value()) {
-    check_dev(*score, "score", at::kFloat);
-    TORCH_CHECK(score->dim() == 1 && score->numel() == n && score->is_contiguous(), "score must be a contiguous [n]");
-    a.score = score->data_ptr<float>();
-  }
-  if (flag.has_value()) {
-    TORCH_CHECK(score.has_value(), "flags need scores");
-    TORCH_CHECK(flag->is_cuda() && (flag->scalar_type() == at::kByte || flag->scalar_type() == at::kBool) && flag->dim() == 1 &&
-                    flag->numel() == n && flag->is_contiguous(), "flag must be a contiguous device uint8 / bool [n]");
-    a.flag = static_cast<uint8_t*>(flag->data_ptr());
-  }
   a.threshold = (float)threshold;
-  if (y.has_value()) {
-    check_dev(*y, "y", at::kFloat);
-    TORCH_CHECK(sums && !score.has_value(), "own targets are for sums alone");
-    TORCH_CHECK(y->dim() == 2 && y->size(0) == n && y->size(1) == O && (O == 1 || y->stride(1) == 1) &&
-                    (n == 1 || y->stride(0) >= O), "y must be [n, ", O, "] rows with contiguous features");
-    a.y = y->data_ptr<float>();
-    a.ldy = n == 1 ? O : y->stride(0);
-  }
-  TORCH_CHECK(rec.has_value() || score.has_value() || sums, "nothing to compute");
-  TORCH_CHECK(max_blocks >= 0 && max_blocks < (1 << 20), "bad max_blocks");
-  TORCH_CHECK(tile == 0 || tile == sml::DFWW_ROWS_SMALL || tile == sml::DFWW_ROWS_LARGE, "tile must be 0, 64 or 128");
-  a.max_blocks = (int)max_blocks;
   a.tile = (int)tile;
   c10::hip::HIPGuard guard(x.device().index());
   c10::optional<at::Tensor> part;
@@ -1393,8 +1352,6 @@ c10::optional<std::tuple<at::Tensor, at::Tensor>> dense_forward_fleet(
   check_dev(images, "images", at::kFloat);
   TORCH_CHECK(images.dim() == 2 && images.is_contiguous() && images.device() == x.device(),
               "images must be a contiguous fp32 [M, stride] on x's device");
-  for (const c10::optional<at::Tensor>* t : {&scale, &shift, &rec, &score, &flag, &thr, &y})
-    TORCH_CHECK(!t->has_value() || (*t)->device() == x.device(), "every tensor must live on x's device");
   const int64_t M = images.size(0);
   sml::DenseFleetFwdArgs a{};
   a.nl = dense_fwd_table(table, a.L);
@@ -1405,22 +1362,16 @@ c10::optional<std::tuple<at::Tensor, at::Tensor>> dense_forward_fleet(
   const int64_t* host = sized ? fleet_rows_table(rows_table, M) : nullptr;
   const bool laid = a.nl >= 1 && a.nl <= sml::DFW_MAXLAYERS;
   const int64_t want_floats = laid ? a.L[a.nl - 1].b_off + sml::dfw_pad16(a.L[a.nl - 1].out) : 0;
-  const std::string why = sml::dense_fleet_fwd_check(a.L, a.nl, a.nl ? a.L[0].in : 0, want_floats, scored, M, host, n,
-                                                     images.size(1));
-  TORCH_CHECK(why.empty(), "dense_forward_fleet: ", why);
-  a.D = a.L[0].in;
-  const int64_t O = a.L[a.nl - 1].out;
-  TORCH_CHECK(n >= 1 && x.size(1) == a.D && (a.D == 1 || x.stride(1) == 1) && (n == 1 || x.stride(0) >= a.D),
-              "x must be [n >= 1, ", a.D, "] rows with contiguous features");
+  dense_fwd_io(a, "dense_forward_fleet",
+               sml::dense_fleet_fwd_check(a.L, a.nl, a.nl ? a.L[0].in : 0, want_floats, scored, M, host, n, images.size(1)), x,
+               scale, shift, rec, score, flag, score.has_value() && thr.has_value(), "flags need scores and thresholds", sums, y,
+               max_blocks, &thr);
   for (const at::Tensor* t : {&rows_table_dev, &pair_base_dev})
     TORCH_CHECK(t->is_cuda() && t->device() == x.device() && t->scalar_type() == at::kLong && t->is_contiguous(),
                 "rows_table_dev / pair_base_dev must be contiguous int64 on x's device");
   TORCH_CHECK(rows_table_dev.numel() == 2 * M && pair_base_dev.numel() == M + 1, "rows_table_dev [M, 2], pair_base_dev [M + 1]");
   std::vector<int64_t> pb(M + 1);
   sml::dense_fleet_fwd_pair_base(host, M, pb.data());
-  a.x = x.data_ptr<float>();
-  a.ldx = n == 1 ? a.D : x.stride(0);
-  a.n = n;
   a.images = images.data_ptr<float>();
   a.stride = images.size(1);
   a.img_floats = (int)want_floats;
@@ -1428,46 +1379,11 @@ c10::optional<std::tuple<at::Tensor, at::Tensor>> dense_forward_fleet(
   a.table = rows_table_dev.data_ptr<int64_t>();
   a.pair_base = pair_base_dev.data_ptr<int64_t>();
   a.pairs = pb[M];
-  TORCH_CHECK(scale.has_value() == shift.has_value(), "scale and shift come together");
-  if (scale.has_value()) {
-    check_dev(*scale, "scale", at::kFloat);
-    check_dev(*shift, "shift", at::kFloat);
-    TORCH_CHECK(scale->numel() == a.D && shift->numel() == a.D && scale->is_contiguous() && shift->is_contiguous(),
-                "scale / shift must have ", a.D, " entries");
-    a.scale = scale->data_ptr<float>();
-    a.shift = shift->data_ptr<float>();
-  }
-  if (rec.has_value()) {
-    check_dev(*rec, "rec", at::kFloat);
-    TORCH_CHECK(rec->dim() == 2 && rec->size(0) == n && rec->size(1) == O && rec->is_contiguous(),
-                "rec must be a contiguous [n, ", O, "]");
-    a.rec = rec->data_ptr<float>();
-  }
-  if (score.has_value()) {
-    check_dev(*score, "score", at::kFloat);
-    TORCH_CHECK(score->dim() == 1 && score->numel() == n && score->is_contiguous(), "score must be a contiguous [n]");
-    a.score = score->data_ptr<float>();
-  }
   if (flag.has_value()) {
-    TORCH_CHECK(score.has_value() && thr.has_value(), "flags need scores and thresholds");
-    TORCH_CHECK(flag->is_cuda() && (flag->scalar_type() == at::kByte || flag->scalar_type() == at::kBool) && flag->dim() == 1 &&
-                    flag->numel() == n && flag->is_contiguous(), "flag must be a contiguous device uint8 / bool [n]");
     check_dev(*thr, "thr", at::kFloat);
     TORCH_CHECK(thr->numel() == M && thr->is_contiguous(), "thr must be a contiguous [M]");
-    a.flag = static_cast<uint8_t*>(flag->data_ptr());
     a.thr = thr->data_ptr<float>();
   }
-  if (y.has_value()) {
-    check_dev(*y, "y", at::kFloat);
-    TORCH_CHECK(sums && !score.has_value(), "own targets are for sums alone");
-    TORCH_CHECK(y->dim() == 2 && y->size(0) == n && y->size(1) == O && (O == 1 || y->stride(1) == 1) &&
-                    (n == 1 || y->stride(0) >= O), "y must be [n, ", O, "] rows with contiguous features");
-    a.y = y->data_ptr<float>();
-    a.ldy = n == 1 ? O : y->stride(0);
-  }
-  TORCH_CHECK(rec.has_value() || score.has_value() || sums, "nothing to compute");
-  TORCH_CHECK(max_blocks >= 0 && max_blocks < (1 << 20), "bad max_blocks");
-  a.max_blocks = (int)max_blocks;
   a.plain_copy = plain_copy ? 1 : 0;
   c10::optional<std::tuple<at::Tensor, at::Tensor>> out;
   if (a.pairs < 1) {   // no model has rows: nothing to launch

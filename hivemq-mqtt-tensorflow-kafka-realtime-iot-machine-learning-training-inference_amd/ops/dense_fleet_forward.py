@@ -22,7 +22,7 @@ import torch
 
 from . import dense_forward as dfw
 from ._ext import load_c
-from .serve import _resolve_normalizer, dense_layer_table
+from .serve import dense_layer_table
 
 IMG_ALIGN = 256               # floats: image stride and LDS image buffers are whole 1 KiB chunks
 MAX_MODELS = (1 << 24) - 1
@@ -71,14 +71,7 @@ def check_shape(widths, activations, score: bool, n_models: int) -> str:
 def supports(model, n_models: int = 1, score: bool = False) -> Tuple[bool, str]:
     """(True, "") if the kernel runs a fleet of ``n_models`` stacks shaped like ``model``, else (False, the
     limit it exceeds).  Needs no device."""
-    try:
-        layers = dense_layer_table(model)[0]
-    except ValueError as e:
-        return False, str(e)
-    if not layers:
-        return False, "the model has no Dense layer"
-    why = check_shape([layers[0][0]] + [l[1] for l in layers], [l[2] for l in layers], score, n_models)
-    return (not why), why
+    return dfw._supports(lambda: dense_layer_table(model)[0], lambda w, a: check_shape(w, a, score, n_models))
 
 
 def _state(fleet) -> dict:
@@ -147,15 +140,10 @@ def _rows_tables(fleet, table, n_rows: int, per_row: bool):
 
 
 def _normalizer(fleet, normalizer, D: int):
-    cache = _state(fleet)["norm"]
-    key = normalizer if normalizer is None or isinstance(normalizer, str) else None
-    if key in cache and (key is not None or normalizer is None):
-        return cache[key]
-    sc, sh = _resolve_normalizer(normalizer, D, fleet._template, "the models have")
-    out = (None, None) if sc is None else (torch.from_numpy(sc).to(fleet.device), torch.from_numpy(sh).to(fleet.device))
-    if normalizer is None or isinstance(normalizer, str):
-        cache[key] = out
-    return out
+    """The two named normalisers are cached on the fleet (it has one device)."""
+    named = normalizer is None or isinstance(normalizer, str)
+    return dfw._cached_normalizer(_state(fleet)["norm"] if named else None, normalizer, normalizer, D, fleet._template,
+                                  "the models have", fleet.device)
 
 
 def _prepare(fleet, x, table, score: bool, per_row: bool):

@@ -1,6 +1,6 @@
 """The fused bulk forward's limits and weight image on the CPU (``ops/dense_forward.py``: the Python
-mirror of ``csrc/include/sml_dense_fwd_plan.h``; tests/test_dense_forward_gpu.py holds the two checks
-together through the extension)."""
+mirror of ``csrc/include/sml_dense_fwd_plan.h``; tests/test_dense_forward_check.py holds the two checks
+together on the CPU, tests/test_dense_forward_gpu.py through the extension)."""
 import numpy as np
 import pytest
 

@@ -1,6 +1,6 @@
 """The wide fused bulk forward's limits and bf16 weight image on the CPU (``ops/dense_forward_wide.py``:
-the Python mirror of ``csrc/include/sml_dense_fwdw_plan.h``; tests/test_dense_forward_wide_gpu.py holds
-the two checks together through the extension)."""
+the Python mirror of ``csrc/include/sml_dense_fwdw_plan.h``; tests/test_dense_forward_check.py holds the
+two checks together on the CPU, tests/test_dense_forward_wide_gpu.py through the extension)."""
 import numpy as np
 import pytest
 
