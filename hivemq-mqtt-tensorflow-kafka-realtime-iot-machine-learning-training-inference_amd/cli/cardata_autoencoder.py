@@ -50,10 +50,10 @@ def _flags(p):
                    help="hidden widths of a Dense stack, e.g. 64,16,64 (18 in, 18 out; tanh / relu alternate, relu "
                         "last): trains an nn.Sequential instead of the 18-14-7-7-18 autoencoder and saves a Keras "
                         ".h5 that `serve --model dense` accepts; with it, predict loads the file as such a stack")
-    p.add_argument("--engine", default="auto", choices=["auto", "persistent", "layers", "throughput"],
+    p.add_argument("--engine", default="auto", choices=["auto", "persistent", "layers", "throughput", "wide"],
                    help="with --layers: the trainer nn.Model.fit runs; throughput is the large-batch step (two "
                         "launches per step, any batch size), which trains on the first --take batches held as "
-                        "one array, in the stream's order")
+                        "one array, in the stream's order; wide is that step for widths up to 512 (four launches)")
     p.add_argument("--predict-engine", default="auto", choices=["auto", "fused", "layers", "wide"],
                    help="predict --layers: the forward nn.Model.predict runs; fused is the fp32 one-launch kernel "
                         "(widths up to 128), wide the bf16 one (widths up to 512), layers the layer loop; fused and "
@@ -127,7 +127,7 @@ def _train_layers(ns, servers, cfg, epochs, batch_size, out_path):
     training = _stream(ns, servers, cfg).filter_normal(device=True).normalize()
     t0 = time.perf_counter()
     shuffle = True
-    if ns.engine == "throughput":   # that engine takes arrays, not a Stream: the epoch's rows, once
+    if ns.engine in ("throughput", "wide"):   # these engines take arrays, not a Stream: the epoch's rows, once
         training = next(iter(training.batch(int(ns.take) * int(batch_size)))).x
         shuffle = False
     model.fit(training, epochs=epochs, batch_size=batch_size, steps_per_epoch=ns.take, verbose=2, engine=ns.engine,

@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "sml_dense_batch.h"
+#include "sml_dense_batchw.h"
 #include "sml_dense_fleet_serve.h"
 #include "sml_dense_fleet_fwd.h"
 #include "sml_dense_fwd_plan.h"
@@ -464,6 +465,37 @@ struct DenseBatchApplyArgs {
 };
 hipError_t dense_batch_apply_launch(const DenseBatchApplyArgs& args, hipStream_t stream);
 int dense_batch_cus();   // of the current device
+
+// ---- large-batch train step of a WIDE Dense stack, widths up to 512 (dense_batch_wide.hip) ----
+// dense_batchw_launch records the step's three launches: the two bf16 images from the masters; G
+// workgroups running forward and backward over their spans of 64-row tiles (bf16 operands into `ws`,
+// bias-gradient partials and a [loss, correct] pair per workgroup); one grouped weight-gradient launch
+// over `items` that fills slab[0 .. S - 1][nflat] and pairs[0 .. S - 1][2].  dense_batch_apply_launch
+// with G = S finishes the step.  The plan, the limits and dense_batchw_check are in sml_dense_batchw.h.
+struct DenseBatchWArgs {
+  const float* flat;   // fp32 masters, 16-byte aligned, read only
+  const float* x;
+  int64_t ldx;
+  const float* y;      // null: y = x
+  int64_t ldy;
+  const int32_t* order;
+  int64_t n, row0;     // samples; the step's first
+  int batch;           // rows of THIS step, row0 + batch <= n; the plan is this batch's
+  int nl, D, nflat;
+  int G, S;            // forward / backward workgroups; row splits
+  DenseMBLayer L[DMB_MAXLAYERS];
+  DenseBatchWPlan P;
+  uint16_t* image;     // [P.img_words]
+  uint16_t* ws;        // [P.ws_words]
+  float* slots;        // [G][P.slot_floats]
+  float* dbp;          // [G][P.ndb]
+  float* wpairs;       // [G][2]
+  const int32_t* items;   // device [nitems][4]: layer (or -1: the bias item), first input, first unit, split
+  int nitems;          // S * (P.wtiles + 1)
+  float* slab;         // [S][nflat], zero where no parameter lives
+  float* pairs;        // [S][2]
+};
+hipError_t dense_batchw_launch(const DenseBatchWArgs& args, hipStream_t stream);
 
 // ---- fused bulk forward of a Dense stack (dense_forward.hip) ----
 // One launch runs the whole stack over n rows: rows are read once, activations chain from layer to

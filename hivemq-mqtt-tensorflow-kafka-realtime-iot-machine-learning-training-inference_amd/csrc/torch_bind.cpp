@@ -1673,6 +1673,168 @@ std::tuple<at::Tensor, at::Tensor> dense_batch_grad(const at::Tensor& flat, cons
   return std::make_tuple(grad, out);
 }
 
+// ---- the wide variant (dense_batch_wide.hip, sml_dense_batchw.h) ----
+
+// Empty when dense_batch_wide.hip can run a step of this batch on the stack, else the limit it exceeds.
+std::string dense_batchw_check(const std::vector<std::vector<double>>& table, int64_t batch, int64_t nflat,
+                               bool own_targets) {
+  if (table.empty() || table.size() > (size_t)sml::DBW_MAXLAYERS)
+    return sml::dense_batchw_check(nullptr, (int)table.size(), 0, batch, nflat, own_targets);
+  sml::DenseMBLayer L[sml::DMB_MAXLAYERS] = {};
+  const int nl = dense_mb_table(table, L);
+  return sml::dense_batchw_check(L, nl, L[0].in, batch, nflat < 0 ? INT64_MAX : nflat, own_targets);
+}
+
+// What dense_batchw_train and dense_batchw_grad share: the checks, the launch arguments, the buffers
+// (allocated once per call for the largest step) and the sequence of a step's launches.  The plan, the
+// grids and the weight-gradient table depend on a step's rows, so a partial last step gets its own.
+struct DenseBatchWCall {
+  sml::DenseBatchWArgs g{};
+  sml::DenseBatchApplyArgs ap{};
+  at::Tensor image, ws, slots, dbp, wpairs, slab, pairs, items[2];
+  int groups = 0, splits = 0, cus = 0, items_rows[2] = {0, 0};
+  int64_t batch = 0;
+
+  // fills g's plan, grids and table for a step of `rows` rows; the tables of the (at most two) step
+  // sizes of a call are built and copied to the device on first use
+  void shape(int rows, const at::Tensor& like) {
+    g.batch = rows;
+    g.P = sml::dense_batchw_plan(g.L, g.nl, rows);
+    g.G = sml::dense_batchw_groups(rows, groups, cus);
+    g.S = sml::dense_batchw_splits(rows, splits, cus, g.P.wtiles);
+    g.nitems = g.S * (g.P.wtiles + 1);
+    const int k = rows == (int)batch ? 0 : 1;
+    if (items_rows[k] != rows) {
+      std::vector<int32_t> t;
+      t.reserve((size_t)g.nitems * 4);
+      for (int s = 0; s < g.S; ++s) {
+        for (int l = 0; l < g.nl; ++l)
+          for (int i0 = 0; i0 < g.L[l].in; i0 += sml::DBW_WTILE)
+            for (int j0 = 0; j0 < g.L[l].units; j0 += sml::DBW_WTILE) t.insert(t.end(), {l, i0, j0, s});
+        t.insert(t.end(), {-1, 0, 0, s});
+      }
+      items[k] = at::tensor(t, at::kInt).to(like.device());
+      items_rows[k] = rows;
+    }
+    g.items = items[k].data_ptr<int32_t>();
+  }
+
+  DenseBatchWCall(const char* who, const at::Tensor& flat, const std::vector<std::vector<double>>& table,
+                  const at::Tensor& x, const c10::optional<at::Tensor>& y, const c10::optional<at::Tensor>& order,
+                  int64_t row0, int64_t batch_, int64_t groups_, int64_t splits_) {
+    check_dev(flat, "flat", at::kFloat);
+    check_dev(x, "x", at::kFloat);
+    TORCH_CHECK(flat.is_contiguous() && flat.numel() % 4 == 0 && flat.numel() < (1 << 30) &&
+                    reinterpret_cast<uintptr_t>(flat.data_ptr<float>()) % 16 == 0,
+                who, ": flat must be contiguous, 16-byte aligned and a multiple of 4 floats long");
+    const sml::DenseMBArgs r = dense_mb_rows({who, "n", "permutation of the n samples"}, table,
+                                             dense_batchw_check(table, batch_, flat.numel(), y.has_value()), x, y, order,
+                                             batch_, sml::DMB_BF16);
+    const int64_t n = x.size(0);
+    TORCH_CHECK(row0 >= 0 && row0 < n, who, ": row0 ", row0, " is outside the ", n, " rows of x");
+    TORCH_CHECK(groups_ >= 0 && groups_ < (1 << 30) && splits_ >= 0 && splits_ < (1 << 30), who, ": bad groups ", groups_,
+                " / splits ", splits_);
+    g.flat = flat.data_ptr<float>();
+    g.x = r.x;
+    g.ldx = r.ldx;
+    g.y = r.y;
+    g.ldy = r.ldy;
+    g.order = r.order;
+    g.n = n;
+    g.nl = r.nl;
+    g.D = r.D;
+    g.nflat = (int)flat.numel();
+    std::copy(r.L, r.L + sml::DMB_MAXLAYERS, g.L);
+    batch = batch_;
+    groups = (int)groups_;
+    splits = (int)splits_;
+    cus = sml::dense_batch_cus();
+    shape((int)std::min(batch, n - row0), flat);   // the call's largest step
+    const auto words = x.options().dtype(at::kShort);
+    image = at::empty({g.P.img_words}, words);
+    ws = at::empty({g.P.ws_words}, words);
+    slots = at::empty({g.G, std::max(g.P.slot_floats, 4)}, flat.options());
+    dbp = at::empty({g.G, g.P.ndb}, flat.options());
+    wpairs = at::empty({g.G, 2}, flat.options());
+    slab = at::zeros({g.S, flat.numel()}, flat.options());
+    pairs = at::zeros({g.S, 2}, flat.options());
+    g.image = reinterpret_cast<uint16_t*>(image.data_ptr<int16_t>());
+    g.ws = reinterpret_cast<uint16_t*>(ws.data_ptr<int16_t>());
+    g.slots = slots.data_ptr<float>();
+    g.dbp = dbp.data_ptr<float>();
+    g.wpairs = wpairs.data_ptr<float>();
+    g.slab = slab.data_ptr<float>();
+    g.pairs = pairs.data_ptr<float>();
+    ap.slab = g.slab;
+    ap.pairs = g.pairs;
+    ap.nflat = g.nflat;
+  }
+
+  // the four launches of the step that starts at sample r0; ap's targets are the caller's
+  void step(int64_t r0, const at::Tensor& like, hipStream_t stream) {
+    g.row0 = r0;
+    shape((int)std::min(batch, g.n - r0), like);
+    ap.G = g.S;
+    SML_CHECK_HIP(sml::dense_batchw_launch(g, stream));
+    SML_CHECK_HIP(sml::dense_batch_apply_launch(ap, stream));
+  }
+};
+
+// nsteps consecutive Keras steps of a wide Dense stack (dense_batch_wide.hip): four launches a step on
+// the current stream, no host synchronisation; the arguments and the result of dense_batch_train.
+// groups: forward / backward workgroups of a step (0: one per CU); splits: row splits of the weight
+// gradients (0: the kernel's choice); both are clamped to what the step's rows allow.
+at::Tensor dense_batchw_train(const at::Tensor& flat, const at::Tensor& m, const at::Tensor& v, const at::Tensor& iter,
+                              const std::vector<std::vector<double>>& table, const at::Tensor& x,
+                              const c10::optional<at::Tensor>& y, const c10::optional<at::Tensor>& order, int64_t row0,
+                              int64_t batch, int64_t nsteps, double lr, double beta1, double beta2, double eps,
+                              int64_t groups, int64_t splits) {
+  check_dev(m, "m", at::kFloat);
+  check_dev(v, "v", at::kFloat);
+  TORCH_CHECK(iter.is_cuda() && iter.scalar_type() == at::kLong && iter.numel() == 1, "iter must be a device int64[1]");
+  TORCH_CHECK(m.is_contiguous() && v.is_contiguous() && m.numel() == flat.numel() && v.numel() == flat.numel(),
+              "flat / m / v must be contiguous and of one size");
+  TORCH_CHECK(nsteps >= 1 && nsteps < (1 << 30), "bad nsteps");
+  check_dev(x, "x", at::kFloat);
+  c10::hip::HIPGuard guard(x.device().index());
+  DenseBatchWCall call("dense_batchw_train", flat, table, x, y, order, row0, batch, groups, splits);
+  auto out = at::zeros({nsteps, 2}, flat.options());
+  const at::Tensor iter0 = iter.clone();   // the count before the first step: no launch writes it
+  call.ap.flat = flat.data_ptr<float>();
+  call.ap.m = m.data_ptr<float>();
+  call.ap.v = v.data_ptr<float>();
+  call.ap.iter = iter.data_ptr<int64_t>();
+  call.ap.iter0 = iter0.data_ptr<int64_t>();
+  call.ap.lr = (float)lr;
+  call.ap.beta1 = (float)beta1;
+  call.ap.beta2 = (float)beta2;
+  call.ap.eps = (float)eps;
+  const int64_t steps = std::min(nsteps, (call.g.n - row0 + batch - 1) / batch);
+  for (int64_t s = 0; s < steps; ++s) {
+    call.ap.step = (int)s;
+    call.ap.out = out.data_ptr<float>() + 2 * s;
+    call.step(row0 + s * batch, flat, cur_stream(x));
+  }
+  return out;
+}
+
+// One step's summed gradient [nflat] (FlatParams order) and its [mean loss, correct rows], parameters
+// untouched: dense_batchw_train's launches with the update switched off.
+std::tuple<at::Tensor, at::Tensor> dense_batchw_grad(const at::Tensor& flat, const std::vector<std::vector<double>>& table,
+                                                     const at::Tensor& x, const c10::optional<at::Tensor>& y,
+                                                     const c10::optional<at::Tensor>& order, int64_t row0, int64_t batch,
+                                                     int64_t groups, int64_t splits) {
+  check_dev(x, "x", at::kFloat);
+  c10::hip::HIPGuard guard(x.device().index());
+  DenseBatchWCall call("dense_batchw_grad", flat, table, x, y, order, row0, batch, groups, splits);
+  auto grad = at::zeros({flat.numel()}, flat.options());
+  auto out = at::zeros({2}, flat.options());
+  call.ap.grad_out = grad.data_ptr<float>();
+  call.ap.out = out.data_ptr<float>();
+  call.step(row0, flat, cur_stream(x));
+  return std::make_tuple(grad, out);
+}
+
 // Fused LSTM Dense head (lstm_head.hip): returns dh = dy . W^T as bf16 [n, 16]; dW / db into grad
 // through map (the dense_wgrad slab layout), this step's [sum sq err, #correct] into acc, out =
 // acc / div, counter + 1.
@@ -2310,6 +2472,21 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("row0") = 0, py::arg("batch") = 1024, py::arg("groups") = 0);
   m.def("dense_batch_check", &dense_batch_check,
         "empty if dense_batch_train can run the table at this batch, else the reason", py::arg("table"),
+        py::arg("batch"), py::arg("nflat") = -1, py::arg("own_targets") = false);
+  m.def("dense_batchw_train", &dense_batchw_train,
+        "wide large-batch trainer: nsteps Keras Adam steps of a Dense stack up to 512 wide (dense_mb_train's table), "
+        "four launches per step on bf16 MFMAs; groups: forward / backward workgroups of a step (0: one per CU); "
+        "splits: row splits of the weight gradients (0: the kernel's choice)",
+        py::arg("flat"), py::arg("m"), py::arg("v"), py::arg("iter"), py::arg("table"), py::arg("x"),
+        py::arg("y") = py::none(), py::arg("order") = py::none(), py::arg("row0") = 0, py::arg("batch") = 1024,
+        py::arg("nsteps") = 1, py::arg("lr") = 1e-3, py::arg("beta1") = 0.9, py::arg("beta2") = 0.999,
+        py::arg("eps") = 1e-7, py::arg("groups") = 0, py::arg("splits") = 0);
+  m.def("dense_batchw_grad", &dense_batchw_grad,
+        "one step of dense_batchw_train without the update -> (summed gradient [nflat], [mean loss, correct rows])",
+        py::arg("flat"), py::arg("table"), py::arg("x"), py::arg("y") = py::none(), py::arg("order") = py::none(),
+        py::arg("row0") = 0, py::arg("batch") = 1024, py::arg("groups") = 0, py::arg("splits") = 0);
+  m.def("dense_batchw_check", &dense_batchw_check,
+        "empty if dense_batchw_train can run the table at this batch, else the reason", py::arg("table"),
         py::arg("batch"), py::arg("nflat") = -1, py::arg("own_targets") = false);
   m.def("dense_mb_train_fleet", &dense_mb_train_fleet,
         "one launch for M Dense stacks of one architecture, one workgroup per model: flat / m / v [M, stride], iter [M], "

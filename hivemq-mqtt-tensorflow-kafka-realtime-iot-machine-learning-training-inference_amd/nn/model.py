@@ -428,13 +428,15 @@ class Model:
         (``ops.dense_batch``: two launches per step on bf16 MFMAs, any batch up to its ``MAX_BATCH``,
         the layer loop's shuffled batches) and raises ``ValueError`` with the reason if it cannot:
         a limit of the stack, no ROCm device, several ranks, a ``Stream`` input, or the recognised
-        autoencoder, which has a throughput engine of its own; ``"auto"`` never picks it."""
-        if engine not in ("auto", "persistent", "layers", "throughput"):
-            raise ValueError(f"engine must be 'auto', 'persistent', 'layers' or 'throughput', not {engine!r}")
+        autoencoder, which has a throughput engine of its own; ``"auto"`` never picks it.
+        ``"wide"`` is the same step for stacks up to 512 wide (``ops.dense_batch_wide``: four
+        launches per step, weights streamed from L2), under the same rules."""
+        if engine not in ("auto", "persistent", "layers", "throughput", "wide"):
+            raise ValueError(f"engine must be 'auto', 'persistent', 'layers', 'throughput' or 'wide', not {engine!r}")
         if not self.compiled:
             self.compile()
-        if self._fused is not None and engine == "throughput":
-            raise ValueError("engine='throughput' cannot run: this model is the recognised 4-layer autoencoder, "
+        if self._fused is not None and engine in ("throughput", "wide"):
+            raise ValueError(f"engine={engine!r} cannot run: this model is the recognised 4-layer autoencoder, "
                              "which has its own throughput engine (models.Autoencoder.fit)")
         if self._fused is not None and engine == "persistent":
             raise ValueError("engine='persistent' cannot run: this model is the recognised 4-layer autoencoder, "
@@ -454,12 +456,12 @@ class Model:
         world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
         rank = dist.get_rank() if world > 1 else 0
         allreduce = allreduce_sum_ if world > 1 else None
-        if engine == "throughput":
-            why = self._persistent_reason(x, y, batch_size, world, throughput=True)
+        if engine in ("throughput", "wide"):
+            why = self._persistent_reason(x, y, batch_size, world, throughput=engine)
             if why:
-                raise ValueError(f"engine='throughput' cannot run: {why}")
+                raise ValueError(f"engine={engine!r} cannot run: {why}")
             return self._fit_persistent(x, y, batch_size, epochs, verbose, callbacks, validation_data, shuffle,
-                                        steps_per_epoch, seed, initial_epoch, throughput=True)
+                                        steps_per_epoch, seed, initial_epoch, throughput=engine)
         if engine != "layers":
             why = self._persistent_reason(x, y, batch_size, world)
             if not why and engine == "auto" and self._fused_arg is False:
@@ -527,11 +529,11 @@ class Model:
     # rows of a Stream staged on the device per launch (rounded down to a multiple of the batch)
     STREAM_SEGMENT_ROWS = 1 << 18
 
-    def _persistent_reason(self, x, y, batch_size, world, throughput: bool = False) -> str:
-        """Empty if ``ops.dense_persistent`` (``throughput``: ``ops.dense_batch``) can run this fit,
-        else why not."""
+    def _persistent_reason(self, x, y, batch_size, world, throughput="") -> str:
+        """Empty if ``ops.dense_persistent`` (``throughput``: ``ops.dense_batch`` for ``"throughput"``,
+        ``ops.dense_batch_wide`` for ``"wide"``) can run this fit, else why not."""
         from ..data.stream import Stream
-        from ..ops import dense_batch, dense_persistent as dpers
+        from ..ops import dense_batch, dense_batch_wide, dense_persistent as dpers
         if self.device.type != "cuda":
             return "it needs a ROCm device"
         if world > 1:
@@ -544,7 +546,8 @@ class Model:
                 return "a Stream carries no targets of its own"
         elif not isinstance(x, (np.ndarray, torch.Tensor, list, tuple)):
             return "the input must be arrays, tensors or a Stream"
-        ok, why = (dense_batch if throughput else dpers).supports(self, batch_size, own_targets=own_targets)
+        op = dense_batch_wide if throughput == "wide" else dense_batch if throughput else dpers
+        ok, why = op.supports(self, batch_size, own_targets=own_targets)
         if not ok:
             return why
         if not isinstance(x, Stream):
@@ -558,14 +561,15 @@ class Model:
         return ""
 
     def _fit_persistent(self, x, y, batch_size, epochs, verbose, callbacks, validation_data, shuffle,
-                        steps_per_epoch, seed, initial_epoch, throughput: bool = False) -> History:
+                        steps_per_epoch, seed, initial_epoch, throughput="") -> History:
         """One ``dense_minibatch`` launch per epoch (per segment of a Stream); the kernel updates
         ``fp.flat / m / v / iter`` in place, so save / predict / evaluate see the trained state.
-        ``throughput``: one ``ops.dense_batch.train_steps`` call per epoch instead (arrays only)."""
+        ``throughput`` (``"throughput"`` / ``"wide"``): one ``ops.dense_batch.train_steps`` /
+        ``ops.dense_batch_wide.train_steps`` call per epoch instead (arrays only)."""
         from ..data.stream import Stream
-        from ..ops import dense_batch, dense_persistent as dpers
+        from ..ops import dense_batch, dense_batch_wide, dense_persistent as dpers
         from ..parallel.fault import maybe_inject_range
-        self.last_fit_engine = "throughput" if throughput else "persistent"
+        self.last_fit_engine = ("wide" if throughput == "wide" else "throughput") if throughput else "persistent"
         B = int(batch_size)
         stream = isinstance(x, Stream)
         # bf16 only where it was asked for and the stack fits the bf16 kernel; never an error
@@ -622,7 +626,8 @@ class Model:
                 if steps > 0:
                     maybe_inject_range(gstep, gstep + steps, 0)
                     if throughput:
-                        results.append(dense_batch.train_steps(self, xd, yd, B, steps, 0, order))
+                        op = dense_batch_wide if throughput == "wide" else dense_batch
+                        results.append(op.train_steps(self, xd, yd, B, steps, 0, order))
                     else:
                         results.append(dpers.train_steps(self, xd, yd, B, steps, 0, order, precision=prec))
                 rows = min(n, steps * B)
