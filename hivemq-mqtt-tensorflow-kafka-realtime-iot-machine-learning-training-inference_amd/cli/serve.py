@@ -22,7 +22,8 @@ only (cardata-v3.py:46) and writes reconstructions (cardata-v3.py:243-249). Here
 (:class:`streamml.ops.serve.ScoringServer`; ``--model lstm``: the per-car forecaster
 :class:`~streamml.ops.serve.LSTMScoringServer`, car key -> device slot in C++; ``--model dense``:
 :class:`~streamml.ops.serve.DenseScoringServer` for a Dense autoencoder of any depth, on both
-the chunked and the low-latency path; ``--model dense-fleet <dir>``: the directory ``fleet --layers``
+the chunked and the low-latency path, ``--precision bf16`` for the bf16 MFMA scorer with the bits of
+``score(engine="wide")``; ``--model dense-fleet <dir>``: the directory ``fleet --layers``
 wrote, every car scored by its own model on one resident
 :class:`~streamml.ops.serve.DenseFleetScoringServer`, car key -> model index from ``index.json``), no launch
 per event -> the same result records formatted in C++ -> one produce per fetch -> commit.
@@ -105,6 +106,9 @@ def _flags(p) -> None:
                         "nn.Model) on the persistent scorer of dense_serve.hip.  dense-fleet: <model-file> is "
                         "the output directory of fleet --layers; every car is scored by the model that "
                         "index.json gives its key, all on one resident scorer (dense_serve_fleet.hip)")
+    p.add_argument("--precision", choices=["fp32", "bf16"], default=None,
+                   help="--model dense: fp32 (default; dense_serve.hip) or bf16 (dense_serve_bf16.hip: the "
+                        "arithmetic and bits of score(engine='wide'), up to 16 events per pass)")
     p.add_argument("--fallback-model", default=None, metavar="NAME",
                    help="--model dense-fleet: score cars that index.json does not name with this member "
                         "(default: drop them, counted as keys_dropped)")
@@ -151,11 +155,11 @@ def _require_servable(model, lanes: int = 1) -> None:
         raise SystemExit(f"--model lstm: the persistent forecaster cannot serve this model: {why}")
 
 
-def _require_dense_servable(model) -> None:
+def _require_dense_servable(model, precision: str = "fp32") -> None:
     """``--model dense``: exit naming the limit the persistent Dense scorer cannot serve, the
     missing ROCm device, or the feature count the cardata normaliser needs."""
     from ..ops.serve import DenseScoringServer
-    ok, why = DenseScoringServer.supports(model)
+    ok, why = DenseScoringServer.supports(model, precision)
     if not ok:
         raise SystemExit(f"--model dense: the persistent scorer cannot serve this model: {why}")
     if model.device.type != "cuda":
@@ -222,7 +226,7 @@ def _serve_low_latency(ns, servers, cfg, model, mine, result_parts, summary, ran
     from ..ops.serve import DenseScoringServer, LSTMScoringServer, ScoringServer
 
     if ns.model == "dense":
-        _require_dense_servable(model)
+        _require_dense_servable(model, ns.precision)
     if model.device.type != "cuda":
         raise SystemExit("--low-latency needs a ROCm device (the persistent scorer)")
     if ns.model == "lstm":
@@ -234,10 +238,11 @@ def _serve_low_latency(ns, servers, cfg, model, mine, result_parts, summary, ran
         scorer = model.server(ns.threshold)
         key_table, unknown = model.key_to_model, model.fallback
     elif ns.model == "dense":
-        scorer = DenseScoringServer(model, threshold=ns.threshold, normalizer="cardata")
+        scorer = DenseScoringServer(model, threshold=ns.threshold, normalizer="cardata", precision=ns.precision)
     else:
         scorer = ScoringServer(model, threshold=ns.threshold)
     with scorer as srv:
+        kernel = srv.kernel if ns.model == "dense" else None
         starts = None
         if ns.from_beginning:
             from ..kafka import KafkaClient
@@ -261,7 +266,7 @@ def _serve_low_latency(ns, servers, cfg, model, mine, result_parts, summary, ran
     if ns.model == "lstm":
         summary.update(model="lstm", keys=st["keys"])
     elif ns.model == "dense":
-        summary.update(model="dense")
+        summary.update(model="dense", kernel=kernel, precision=ns.precision)
     elif ns.model == "dense-fleet":
         summary.update(model="dense-fleet", models=len(model.names), kernel="fleet")
     summary.update(events=st["events"], anomalies=st["anomalies"], skipped=st["skipped"], foreign=st["foreign"],
@@ -295,6 +300,9 @@ def main(argv: Sequence[str]) -> int:
         raise SystemExit("--fallback-model goes with --model dense-fleet")
     if ns.calibrated_thresholds and ns.model != "dense-fleet":
         raise SystemExit("--calibrated-thresholds goes with --model dense-fleet")
+    if ns.precision is not None and ns.model != "dense":
+        raise SystemExit("--precision goes with --model dense")
+    ns.precision = ns.precision or "fp32"
     path = common.model_path(ns.workdir, ns.model_file)
     if ns.model == "dense-fleet":
         if not os.path.isdir(path) and os.path.isdir(ns.model_file):
@@ -313,7 +321,7 @@ def main(argv: Sequence[str]) -> int:
     elif ns.model == "dense":
         from ..nn.model import load_model as load_nn_model
         model = load_nn_model(path, device=device, compile=False)
-        _require_dense_servable(model)
+        _require_dense_servable(model, ns.precision)
     else:
         model = load_model(path, device=device, input_normalizer="cardata")
     if ns.metrics_port and rank == 0:
@@ -356,7 +364,7 @@ def main(argv: Sequence[str]) -> int:
     if ns.model == "dense":
         from ..ops.serve import DenseScoringServer
         dense_srv = DenseScoringServer(model, threshold=ns.threshold, normalizer="cardata",
-                                       slots=max(64, min(ns.max_batch, 4096)))
+                                       slots=max(64, min(ns.max_batch, 4096)), precision=ns.precision)
     if ns.model == "lstm":
         if model.device.type != "cuda":
             raise SystemExit("--model lstm serving needs a ROCm device (the persistent forecaster)")
@@ -447,7 +455,7 @@ def main(argv: Sequence[str]) -> int:
         summary["model"] = "lstm"
         summary["keys"] = len(key_ids)
     if dense_srv is not None:
-        summary.update(model="dense", kernel=dense_srv.kernel)
+        summary.update(model="dense", kernel=dense_srv.kernel, precision=ns.precision)
         dense_srv.close()
     if fleet_srv is not None:
         summary.update(model="dense-fleet", models=fleet_srv.n_models, kernel=fleet_srv.kernel)

@@ -9,6 +9,7 @@
 #include "sml_dense_fleet_fwd.h"
 #include "sml_dense_fwd_plan.h"
 #include "sml_dense_fwdw_plan.h"
+#include "sml_dense_serve_bf16.h"
 #include "sml_dense_mb_plan.h"
 
 namespace sml {
@@ -363,6 +364,27 @@ struct DenseServeArgs {
 // dense_serve_in_lds (inline, there): the whole image goes to LDS: a pure function of the layer
 // table and DSV_LDS_IMAGE_BYTES
 hipError_t dense_serve_launch(const DenseServeArgs& args, hipStream_t stream);
+
+// ---- the same on bf16 MFMAs with the wide bulk forward's image and bits (dense_serve_bf16.hip) ----
+// The limits, the LDS plan and dense_serve_bf16_check are in sml_dense_serve_bf16.h (plain C++); the layer
+// table and the image are the wide forward's (DenseFwdLayer, offsets in 16-bit words).
+struct DenseServeBf16Args {
+  ServeCtl* ctl;
+  const ServeReq* req;
+  ServeResult* res;
+  int nslots;
+  int D;
+  const uint16_t* image;   // the bf16 weight image (device, 16-byte aligned)
+  int img_words;
+  int nl;
+  DenseFwdLayer L[DFWW_MAXLAYERS];
+  const float* scale;  // [D] or null
+  const float* shift;
+  float threshold;
+  uint64_t idle_ticks;
+  uint64_t* stats;     // host-mapped: {passes << 32 | events}, cumulative, stored after each pass
+};
+hipError_t dense_serve_bf16_launch(const DenseServeBf16Args& args, hipStream_t stream);
 
 // ---- persistent per-event scorer for a fleet of Dense stacks (dense_serve_fleet.hip) ----
 // DenseFleetServeArgs and dense_fleet_serve_check: sml_dense_fleet_serve.h

@@ -126,8 +126,8 @@ void ServeRing::upload_affine(const std::vector<float>& scale, const std::vector
   shift_d_ = DeviceBuffer(D_ * sizeof(float), shift.data(), "shift");
 }
 
-template <class Args>
-void ServeRing::fill_dense_args(Args& a, const std::vector<DenseServeLayer>& layers, const ServeStats& stats) const {
+template <class Args, class Layer>
+void ServeRing::fill_dense_args(Args& a, const std::vector<Layer>& layers, const ServeStats& stats) const {
   a.nslots = nslots_;
   a.D = D_;
   a.nl = (int)layers.size();
@@ -190,6 +190,32 @@ DenseServe::DenseServe(int device, int nslots, const std::vector<float>& image,
 }
 
 hipError_t DenseServe::launch_kernel() { return dense_serve_launch(args_, stream_); }
+
+int DenseServeBf16::checked_D(const std::vector<uint16_t>& image, const std::vector<DenseFwdLayer>& layers, int D,
+                              const std::vector<float>& scale, const std::vector<float>& shift) {
+  const std::string why = dense_serve_bf16_check(layers.data(), (int)layers.size(), D, (int64_t)image.size());
+  if (!why.empty()) throw std::invalid_argument("DenseServeBf16: " + why);
+  check_affine(scale, shift, D, "DenseServeBf16");
+  return D;
+}
+
+DenseServeBf16::DenseServeBf16(int device, int nslots, const std::vector<uint16_t>& image,
+                               const std::vector<DenseFwdLayer>& layers, int D, const std::vector<float>& scale,
+                               const std::vector<float>& shift, float threshold, double idle_seconds)
+    : ServeRing(device, nslots, checked_D(image, layers, D, scale, shift), idle_seconds, DSVB_MAXD) {
+  name_ = "DenseServeBf16";
+  DenseServeBf16Args& a = args_;
+  upload_affine(scale, shift, name_);
+  fill_dense_args(a, layers, stats_);
+  a.img_words = (int)image.size();
+  a.threshold = threshold;
+  in_lds_ = dense_serve_bf16_plan(a.L, a.nl).in_lds;
+  img_d_ = DeviceBuffer(image.size() * sizeof(uint16_t), image.data(), "bf16 weight image");
+  a.image = img_d_.as<uint16_t>();
+  launch();
+}
+
+hipError_t DenseServeBf16::launch_kernel() { return dense_serve_bf16_launch(args_, stream_); }
 
 int DenseFleetServe::checked_D(const float* images, int64_t n_models, int64_t stride, int64_t img_floats,
                                const std::vector<DenseServeLayer>& layers, int D, const std::vector<float>& scale,

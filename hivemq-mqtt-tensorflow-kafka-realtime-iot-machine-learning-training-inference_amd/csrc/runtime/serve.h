@@ -120,8 +120,8 @@ class ServeRing {
   void upload_affine(const std::vector<float>& scale, const std::vector<float>& shift, const char* who);
   // the front both Dense scorers' argument structs share (rings, D, layer table, normaliser, idle
   // ticks, stats word); the structs stay two: their layout is part of the kernels
-  template <class Args>
-  void fill_dense_args(Args& a, const std::vector<DenseServeLayer>& layers, const ServeStats& stats) const;
+  template <class Args, class Layer>
+  void fill_dense_args(Args& a, const std::vector<Layer>& layers, const ServeStats& stats) const;
   int device_, nslots_, D_, lanes_;
   double idle_s_;
   ServeCtl* ctl_ = nullptr;      // [lanes]
@@ -190,6 +190,35 @@ class DenseServe : public ServeRing {
   static int checked_D(const std::vector<float>& image, const std::vector<DenseServeLayer>& layers, int D,
                        const std::vector<float>& scale, const std::vector<float>& shift);
   DenseServeArgs args_{};
+  bool in_lds_ = false;
+  ServeStats stats_;
+  DeviceBuffer img_d_;
+};
+
+// The same stacks on bf16 MFMAs (dense_serve_bf16.hip): the wide bulk forward's image and arithmetic, so
+// an event's reconstruction has the bits dense_fwdw_launch gives that row; one lane, up to DSVB_EB
+// events per pass.
+class DenseServeBf16 : public ServeRing {
+ public:
+  // image: the packed bf16 image (ops/dense_forward_wide.py pack_image; sml_dense_fwdw_plan.h), layers:
+  // its table, offsets in 16-bit words
+  DenseServeBf16(int device, int nslots, const std::vector<uint16_t>& image, const std::vector<DenseFwdLayer>& layers,
+                 int D, const std::vector<float>& scale, const std::vector<float>& shift, float threshold,
+                 double idle_seconds);
+  ~DenseServeBf16() override { stop(); }   // before any member frees its buffer
+  // where the resident kernel keeps the image: "bf16-lds" | "bf16-stream"
+  const char* kernel() const { return in_lds_ ? "bf16-lds" : "bf16-stream"; }
+  uint64_t passes() const { return stats_.read(complete_[0]) >> 32; }
+  uint64_t events() const { return stats_.read(complete_[0]) & 0xffffffffull; }
+
+ protected:
+  hipError_t launch_kernel() override;
+
+ private:
+  // every limit, before the base class allocates the rings; returns D
+  static int checked_D(const std::vector<uint16_t>& image, const std::vector<DenseFwdLayer>& layers, int D,
+                       const std::vector<float>& scale, const std::vector<float>& shift);
+  DenseServeBf16Args args_{};
   bool in_lds_ = false;
   ServeStats stats_;
   DeviceBuffer img_d_;

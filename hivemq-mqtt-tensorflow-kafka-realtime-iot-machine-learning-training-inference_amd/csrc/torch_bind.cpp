@@ -2219,6 +2219,25 @@ struct DenseServePy : ServePy {
   sml::DenseServe& dense() { return *static_cast<sml::DenseServe*>(s.get()); }
 };
 
+// image: the wide forward's bf16 image as uint16 words; layers: its table of (in, out, act, w_off, b_off)
+// tuples, offsets in words (sml::DenseFwdLayer).  Key-less, as DenseServe.
+struct DenseServeBf16Py : ServePy {
+  DenseServeBf16Py(int device, int nslots, py::array_t<uint16_t, py::array::c_style | py::array::forcecast> image,
+                   std::vector<std::vector<int>> layers, int D, py::object scale, py::object shift, double threshold,
+                   double idle_seconds) {
+    std::vector<uint16_t> img(image.data(), image.data() + image.size());
+    std::vector<sml::DenseFwdLayer> L;
+    for (const auto& t : layers) {
+      if (t.size() != 5) throw std::invalid_argument("layer descriptor: (in, out, act, w_off, b_off)");
+      L.push_back(sml::DenseFwdLayer{t[0], t[1], t[2], t[3], t[4]});
+    }
+    const auto [sc, sh] = affine_of(scale, shift);
+    c10::hip::HIPGuard guard(device);
+    s = std::make_unique<sml::DenseServeBf16>(device, nslots, img, L, D, sc, sh, (float)threshold, idle_seconds);
+  }
+  sml::DenseServeBf16& dense() { return *static_cast<sml::DenseServeBf16*>(s.get()); }
+};
+
 // images: [M, stride] stacked weight images; layers: the one table of (in, out, act, w_off, b_off)
 // tuples, offsets relative to a model's image; thresholds: [M].  Keyed by the model index:
 // _io.ScoreLoop drives it through c_api()'s infer_keyed with nkeys = M.
@@ -2615,6 +2634,22 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
                              "passes the kernel ran since construction")
       .def_property_readonly("events", [](DenseServePy& p) { return p.dense().events(); },
                              "events those passes served");
+  py::class_<DenseServeBf16Py, ServePy>(m, "DenseServeBf16",
+                                        "persistent per-event scorer for Dense stacks on bf16 MFMAs: the wide bulk "
+                                        "forward's image and bits")
+      .def(py::init<int, int, py::array_t<uint16_t, py::array::c_style | py::array::forcecast>,
+                    std::vector<std::vector<int>>, int, py::object, py::object, double, double>(),
+           py::arg("device"), py::arg("nslots"), py::arg("image"), py::arg("layers"), py::arg("D"),
+           py::arg("scale") = py::none(), py::arg("shift") = py::none(), py::arg("threshold") = 5.0,
+           py::arg("idle_seconds") = 2.0)
+      .def_property_readonly("kernel", [](DenseServeBf16Py& p) { return std::string(p.dense().kernel()); },
+                             "where the resident kernel keeps the weight image: bf16-lds | bf16-stream")
+      .def_property_readonly("passes", [](DenseServeBf16Py& p) { return p.dense().passes(); },
+                             "passes the kernel ran since construction")
+      .def_property_readonly("events", [](DenseServeBf16Py& p) { return p.dense().events(); },
+                             "events those passes served");
+  m.attr("DSVB_EB") = (int)sml::DSVB_EB;
+  m.attr("DSVB_LDS_IMAGE_BYTES") = (int)sml::DSVB_LDS_IMAGE_BYTES;
   py::class_<DenseFleetServePy, ServePy>(
       m, "DenseFleetServe", "persistent per-event scorer for a fleet of Dense stacks: a model index per event")
       .def(py::init<int, int, DenseFleetServePy::farray, int64_t, std::vector<std::vector<int>>, int, py::object,

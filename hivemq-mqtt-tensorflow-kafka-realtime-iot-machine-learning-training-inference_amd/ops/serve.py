@@ -10,7 +10,9 @@ without requests and is relaunched transparently on the next request.
 
 ``DenseScoringServer(model)`` has the same surface for Dense stacks of any depth (1..8 layers
 up to 512 wide: an ``nn.Sequential`` / ``nn.Model`` or an ``Autoencoder``) on a resident
-1024-thread workgroup that serves up to 8 events of a backlog per pass.
+1024-thread workgroup that serves up to 8 events of a backlog per pass; with ``precision="bf16"``
+(``dense_serve_bf16.hip``) the workgroup runs the wide bulk forward's bf16 MFMA arithmetic on its image,
+up to 16 events per pass, and an event's reconstruction has ``ops.dense_forward_wide``'s bits.
 
 ``DenseFleetScoringServer(models)`` serves M such stacks of one shape from ONE resident workgroup
 (``dense_serve_fleet.hip``): every row names the member that scores it -- one model per car, as
@@ -222,20 +224,55 @@ class DenseScoringServer(_DenseServer):
     not depend on how the ring batched it.  ``kernel`` is ``"lds"`` when the packed weights fit
     the CU's LDS (``LDS_IMAGE_BYTES``), else ``"stream"``; ``passes`` / ``events`` count what the
     kernel ran.  ``normalizer``: None, ``"cardata"`` (18 features) or a ``(scale, shift)`` pair;
-    for an ``Autoencoder`` the default is the model's own."""
+    for an ``Autoencoder`` the default is the model's own.
+
+    ``precision="bf16"`` (never chosen on its own) serves the same stacks on ``dense_serve_bf16.hip``:
+    the image, the rounding points and the bits of ``ops.dense_forward_wide`` (``bf16(h) . bf16(W)`` on
+    ``v_mfma_f32_16x16x32_bf16``, fp32 everywhere else), so an event's reconstruction is bit for bit the
+    row ``predict / score(engine="wide")`` computes.  A pass serves up to ``MAX_PASS_BF16`` events;
+    ``kernel`` is ``"bf16-lds"`` (the image fits ``LDS_IMAGE_BYTES_BF16``) or ``"bf16-stream"``."""
 
     MAX_WIDTH = 512
     MAX_FEATURES = 32    # a request slot holds 32 words
     MAX_LAYERS = 8
     MAX_PASS = 8
+    MAX_PASS_BF16 = 16   # the columns of the MFMA
     LDS_IMAGE_BYTES = 92 * 1024
+    LDS_IMAGE_BYTES_BF16 = 122 * 1024
     ACTIVATIONS = ("linear", "relu", "tanh", "sigmoid")
+    PRECISIONS = ("fp32", "bf16")
 
     @staticmethod
-    def supports(model) -> Tuple[bool, str]:
-        """(True, "") if the scorer can serve ``model``, else (False, the limit it exceeds).
-        Mirrors the checks of ``DenseServe``'s constructor; needs no device."""
+    def _precision(precision) -> str:
+        if precision not in DenseScoringServer.PRECISIONS:
+            raise ValueError(f"precision must be 'fp32' or 'bf16', not {precision!r}")
+        return precision
+
+    @staticmethod
+    def _supports_bf16(model) -> Tuple[bool, str]:
+        """``dense_serve_bf16_check`` of ``sml_dense_serve_bf16.h``: the wide forward's rules, then the
+        serving rules."""
+        from . import dense_forward_wide as dfww
         S = DenseScoringServer
+        ok, why = dfww.supports(model)
+        if not ok:
+            return False, why
+        layers, _ = dense_layer_table(model)
+        D = layers[0][0]
+        if D > S.MAX_FEATURES:
+            return False, f"rows must have 1..{S.MAX_FEATURES} features (a request slot holds 32 words; it has {D})"
+        if layers[-1][1] != D:
+            return False, f"the last layer must have one unit per feature ({layers[-1][1]} units, {D} features)"
+        return True, ""
+
+    @staticmethod
+    def supports(model, precision: str = "fp32") -> Tuple[bool, str]:
+        """(True, "") if the scorer can serve ``model`` at ``precision``, else (False, the limit it
+        exceeds).  Mirrors the checks of ``DenseServe``'s / ``DenseServeBf16``'s constructor; needs no
+        device."""
+        S = DenseScoringServer
+        if S._precision(precision) == "bf16":
+            return S._supports_bf16(model)
         try:
             layers, _ = dense_layer_table(model)
         except ValueError as e:
@@ -255,29 +292,42 @@ class DenseScoringServer(_DenseServer):
         return True, ""
 
     @staticmethod
-    def kernel_for(model) -> str:
-        """"lds" | "stream": where the resident kernel will keep the weights of ``model``."""
+    def kernel_for(model, precision: str = "fp32") -> str:
+        """"lds" | "stream" (fp32) or "bf16-lds" | "bf16-stream" (bf16): where the resident kernel will
+        keep the weights of ``model``.  Needs no device."""
+        S = DenseScoringServer
         layers, _ = dense_layer_table(model)
-        return "lds" if 4 * _dense_image_floats(layers) <= DenseScoringServer.LDS_IMAGE_BYTES else "stream"
+        if S._precision(precision) == "bf16":
+            from . import dense_forward_wide as dfww
+            return "bf16-lds" if 2 * dfww.image_table(layers)[1] <= S.LDS_IMAGE_BYTES_BF16 else "bf16-stream"
+        return "lds" if 4 * _dense_image_floats(layers) <= S.LDS_IMAGE_BYTES else "stream"
 
     def __init__(self, model, threshold: float = 5.0, slots: int = 4096, idle_seconds: float = 2.0,
-                 normalizer=None, device: Optional[torch.device] = None):
+                 normalizer=None, device: Optional[torch.device] = None, precision: str = "fp32"):
+        self.precision = self._precision(precision)
         dev = torch.device(device) if device is not None else model.device
         if dev.type != "cuda":
             raise RuntimeError("DenseScoringServer needs a ROCm device (use model.predict on CPU)")
-        ok, why = self.supports(model)
+        ok, why = self.supports(model, precision)
         if not ok:
             raise ValueError(f"DenseScoringServer cannot serve this model: {why}")
         layers, weights = dense_layer_table(model)
-        image, table = dense_serve_image(layers, weights)
         self.D = int(layers[0][0])
         sc, sh = _resolve_normalizer(normalizer, self.D, model, "the model has")
         self.threshold = float(threshold)
         C = load_c()
+        index = dev.index if dev.index is not None else torch.cuda.current_device()
+        if precision == "bf16":
+            from . import dense_forward_wide as dfww
+            image, table = dfww.pack_image(layers, weights)   # the bulk kernel's image: no second packer
+            assert (C.DSVB_EB, C.DSVB_LDS_IMAGE_BYTES) == (self.MAX_PASS_BF16, self.LDS_IMAGE_BYTES_BF16)
+            self._s = C.DenseServeBf16(index, int(slots), image, [list(t) for t in table], self.D, sc, sh,
+                                       float(threshold), float(idle_seconds))
+            return
+        image, table = dense_serve_image(layers, weights)
         assert (C.DSV_MAXW, C.DSV_MAXLAYERS, C.DSV_EB, C.DSV_LDS_IMAGE_BYTES) == (
             self.MAX_WIDTH, self.MAX_LAYERS, self.MAX_PASS, self.LDS_IMAGE_BYTES)
-        self._s = C.DenseServe(dev.index if dev.index is not None else torch.cuda.current_device(), int(slots),
-                               image, [list(t) for t in table], self.D, sc, sh, float(threshold),
+        self._s = C.DenseServe(index, int(slots), image, [list(t) for t in table], self.D, sc, sh, float(threshold),
                                float(idle_seconds))
 
     def score(self, rows) -> Tuple[np.ndarray, np.ndarray]:
