@@ -124,9 +124,18 @@ inline int dense_batchw_splits(int batch, int splits, int cus, int wtiles) {
   return want < ksteps ? want : ksteps;
 }
 
+// the loss head of the step's last layer: none (mean squared error on the layer's own activation), or
+// softmax over its units with sparse categorical cross-entropy against integer labels
+enum : int { DBW_HEAD_NONE = 0, DBW_HEAD_SOFTMAX = 1 };
+constexpr const char* DBW_WHY_HEAD =
+    "a softmax head needs 2..512 units in the last layer, a linear last entry in the table, no penalty on the last "
+    "layer, and labels";
+
 // empty if the step can train the stack at this batch (D inputs, nl layers, parameter offsets inside
-// nflat floats, targets of their own or y = x), else the limit it exceeds
-inline std::string dense_batchw_check(const DenseMBLayer* L, int nl, int D, int64_t batch, int64_t nflat, bool own_targets) {
+// nflat floats, targets of their own or y = x; head: own_targets says that labels came), else the limit
+// it exceeds
+inline std::string dense_batchw_check(const DenseMBLayer* L, int nl, int D, int64_t batch, int64_t nflat, bool own_targets,
+                                      int head = DBW_HEAD_NONE) {
   using std::to_string;
   if (nl < 1 || nl > DBW_MAXLAYERS)
     return to_string(nl) + " Dense layers: the wide trainer takes 1.." + to_string((int)DBW_MAXLAYERS) + " (MAX_LAYERS)";
@@ -144,6 +153,11 @@ inline std::string dense_batchw_check(const DenseMBLayer* L, int nl, int D, int6
         (L[l].has_bias && (L[l].b_off < 0 || (int64_t)L[l].b_off + L[l].units > nflat)))
       return "layer " + to_string(l) + ": parameter offsets outside the flat buffer";
     prev = L[l].units;
+  }
+  if (head != DBW_HEAD_NONE) {
+    const DenseMBLayer& H = L[nl - 1];
+    if (head != DBW_HEAD_SOFTMAX) return "unknown head " + to_string(head);
+    if (H.units < 2 || H.act != 0 || H.l1 != 0.0f || H.l2 != 0.0f || !own_targets) return DBW_WHY_HEAD;
   }
   if (!own_targets && prev != D) return "y = x needs as many output units as inputs";
   if (batch < 1 || batch > DBW_MAXBATCH)

@@ -28,7 +28,8 @@ enum : int {
   DFWW_ROWS_SMALL = 64,        // rows of a workgroup's tile: 4 or 8 MFMA row tiles
   DFWW_ROWS_LARGE = 128,
   DFWW_ROW_PAD = 8,            // words added to an activation row in LDS (16-byte aligned, off the bank stride)
-  DFWW_PART_WORDS = 5,         // a wave's epilogue partial of a row: squared error, (max, argmax) of y and of the target
+  DFWW_PART_WORDS = 5,         // a wave's epilogue partial of a row: squared error, (max, argmax) of y and of the target;
+                               // under a softmax head (max, argmax) of its logits, sum of exp(z - max), the label's logit
   DFWW_LDS_BYTES = 160 * 1024,
   DFWW_STATIC_LDS = 2048       // the kernel's own static LDS
 };
@@ -75,10 +76,15 @@ static_assert(DFWW_ROWS_LARGE * (DFWW_MAXW + DFWW_ROW_PAD) * 2 + DFWW_STATIC_LDS
 
 // empty if the kernel takes the stack (D inputs, nl layers whose image offsets lie inside img_words
 // words, or anywhere if that is negative; score: the target is the input row, so out == D), else the
-// limit it exceeds
-inline std::string dense_fwdw_check(const DenseFwdLayer* L, int nl, int D, int64_t img_words, bool score) {
+// limit it exceeds.  head: 0, or 1 for softmax over the last layer's units (its table entry is linear)
+constexpr const char* DFWW_WHY_HEAD_SCORE = "scores need a reconstruction, not a softmax head";
+constexpr const char* DFWW_WHY_HEAD = "a softmax head needs 2..512 units in the last layer and a linear last entry in the table";
+inline std::string dense_fwdw_check(const DenseFwdLayer* L, int nl, int D, int64_t img_words, bool score, int head = 0) {
+  if (head != 0 && score) return DFWW_WHY_HEAD_SCORE;
   const std::string why = dense_fwd_check_rows(L, nl, D, score, DFWW_MAXW, "wide fused");
-  return why.empty() ? dense_fwd_check_image(L, nl, img_words, 32, 2, "words") : why;
+  if (!why.empty()) return why;
+  if (head != 0 && (head != 1 || L[nl - 1].out < 2 || L[nl - 1].act != 0)) return DFWW_WHY_HEAD;
+  return dense_fwd_check_image(L, nl, img_words, 32, 2, "words");
 }
 
 }  // namespace sml

@@ -516,6 +516,8 @@ struct DenseBatchWArgs {
   int nitems;          // S * (P.wtiles + 1)
   float* slab;         // [S][nflat], zero where no parameter lives
   float* pairs;        // [S][2]
+  const int32_t* labels;   // [n] class of every sample under head = DBW_HEAD_SOFTMAX (y is null then), else null
+  int head;            // DBW_HEAD_NONE: mean squared error; DBW_HEAD_SOFTMAX: softmax + sparse categorical cross-entropy
 };
 hipError_t dense_batchw_launch(const DenseBatchWArgs& args, hipStream_t stream);
 
@@ -611,6 +613,8 @@ struct DenseFwdWArgs {
   int max_blocks;          // 0: as many workgroups as the CUs hold
   int tile;                // rows of a workgroup's tile: 64, 128 or 0 (the kernel's choice)
   DenseFwdLayer L[DFW_MAXLAYERS];
+  const int32_t* labels;   // [n] classes for sums under a head, or null
+  int head;                // 1: softmax over the last layer's units: rec = probabilities, sums = [cross-entropy, correct rows]
 };
 // workgroups dense_fwdw_launch starts for n >= 1 rows of a stack that passes dense_fwdw_check
 int dense_fwdw_grid(const DenseFwdLayer* L, int nl, int64_t n, int max_blocks, int tile);

@@ -35,6 +35,19 @@
 //    by xor 1, 2, 4, 8, and lane c = 0 adds into the workgroup's fp32 LDS array.  One partial per
 //    workgroup leaves at the end, with its [loss, correct] pair (sums kept in doubles per thread and
 //    folded in index order).
+//    SOFTMAX HEAD (a.head = DBW_HEAD_SOFTMAX, the kernel's second instance; sml_dense_head.h): the last
+//    layer is linear in the table and its loss is sparse categorical cross-entropy against a.labels
+//    (int32 per sample, addressed through order / row0 as target rows are; a.y is null).  A row's
+//    softmax spans the eight waves, so the epilogue is an online-softmax merge through s_part with ONE
+//    more barrier: per wave and row (max, argmax, sum exp(z - max), the label's logit), a wave without a
+//    block writing the neutral element; after the barrier every lane merges the eight partials of its
+//    rows in wave order and forms dz = (p - [u == label]) / batch from the logits still in its
+//    accumulators.  bf16 dz to LDS and the workspace, unrounded column sums and the zero-fill are the
+//    squared-error path's; the row's thread adds log S + M - z_label and the argmax match, and the
+//    workgroup's loss is their sum / batch + penalties / batch.  Padded units take no part, a row past
+//    `live` gets dz = 0.  The accumulators live across that barrier: the instance without a head keeps
+//    the 153 VGPRs it had (layer<1>, <2> and <4> are inlined into one kernel, so the count is the
+//    kernel's: 153 before the head existed, 153 / 161 without / with it now); neither uses scratch.
 //    Rows past the batch are staged as zero and their dz is zero; padded k and units meet zero weights
 //    only; with an odd number of unit blocks the wave that would own the next block zero-fills it, in
 //    both directions.
@@ -50,6 +63,7 @@
 
 #include "sml_common.h"
 #include "sml_dense_fwd_launch.h"
+#include "sml_dense_head.h"
 #include "sml_ops.h"
 
 namespace sml {
@@ -70,12 +84,6 @@ __device__ __forceinline__ int opaque(int v) {
 __device__ __forceinline__ int uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
 __device__ __forceinline__ f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
 __device__ __forceinline__ void st4(float* p, f32x4 v) { *reinterpret_cast<f32x4*>(p) = v; }
-__device__ __forceinline__ void take_max(float& b, int& i, float ob, int oi) {
-  if (ob > b || (ob == b && oi < i)) {
-    b = ob;
-    i = oi;
-  }
-}
 __device__ __forceinline__ float pen_grad(float l1, float l2, float h, float inv_rows) {
   const float sg = h > 0.0f ? 1.0f : h < 0.0f ? -1.0f : 0.0f;
   return (l1 * sg + 2.0f * l2 * h) * inv_rows;
@@ -203,7 +211,7 @@ __device__ __forceinline__ void mfma_loop(const uint16_t* img, const float* bias
 // One contraction over the tile and what follows it.  Forward (bwd false): layer l's output from its
 // input; a hidden layer's h goes back to LDS (and to the slot), the last layer's becomes dz_L.
 // Backward: dz_{l-1} from dz_l.  `lo` is the layer whose output units the accumulators hold.
-template <int UBN>
+template <int UBN, bool HEAD>
 __device__ __forceinline__ void layer(const DenseBatchWArgs& a, const Tile& T, int l, bool bwd, int tid, double& lsum,
                                       double& lcnt, double& lpen) {
   const int lane = opaque(tid) & 63, wid = tid >> 6, c = lane & 15, g = lane >> 4;
@@ -213,10 +221,26 @@ __device__ __forceinline__ void layer(const DenseBatchWArgs& a, const Tile& T, i
   const int nub = (N + 15) >> 4, np = 16 * nub, S = a.P.stride;
   const float l1 = a.L[lo].l1, l2 = a.L[lo].l2;
   const bool pen = l1 != 0.0f || l2 != 0.0f, last = !bwd && l == a.nl - 1, is_dz = bwd || last;
+  const bool head = HEAD && last;
   f32x4 acc[RT][UBN];
   mfma_loop<UBN>(a.image + (bwd ? a.P.L[l].tw : a.P.L[l].fw),
                  bwd ? nullptr : reinterpret_cast<const float*>(a.image + a.P.L[l].fb), K, N, T.s_act, S, lane, wid, acc);
   __syncthreads();   // every wave has read the contraction's input: the tile is free
+
+  int lab[RT];
+  if (head) {   // uniform: every wave's partial of every row, then the head's one barrier
+#pragma unroll
+    for (int t = 0; t < RT; ++t) {
+      const int rr = 16 * t + c;
+      lab[t] = -1;
+      if (rr < T.live) {
+        const int64_t pos = T.pos0 + rr;
+        lab[t] = a.labels[a.order ? (int64_t)a.order[pos] : pos];
+      }
+      head_wave_partial<UBN>(acc[t], wid, nub, N, lab[t], lane, T.s_part + (wid * R + rr) * DFWW_PART_WORDS);
+    }
+    __syncthreads();
+  }
 
   f32x4 dbs[UBN];
 #pragma unroll
@@ -227,7 +251,9 @@ __device__ __forceinline__ void layer(const DenseBatchWArgs& a, const Tile& T, i
     const int rr = 16 * t + c;
     const bool rlive = rr < T.live;
     const float* trow = nullptr;
-    if (last && rlive) {
+    DenseHeadRow hr = {};
+    if (head) hr = head_merge(T.s_part, R, rr);
+    if (last && !head && rlive) {
       const int64_t pos = T.pos0 + rr, smp = a.order ? (int64_t)a.order[pos] : pos;
       trow = a.y ? a.y + smp * a.ldy : a.x + smp * a.ldx;
     }
@@ -255,6 +281,13 @@ __device__ __forceinline__ void layer(const DenseBatchWArgs& a, const Tile& T, i
             if (!last) {
               if (Po.slot >= 0) st4(T.slot + Po.slot + rr * np + u0, h);
               v = h;
+            } else if (head) {   // dz = (p - [u == label]) / batch from the logits the accumulators still hold
+#pragma unroll
+              for (int r = 0; r < 4; ++r) {
+                const int u = u0 + r;
+                const float p = head_prob(acc[t][j][r], hr) - (u == lab[t] ? 1.0f : 0.0f);
+                v[r] = (rlive && u < N) ? p * T.inv_rows : 0.0f;
+              }
             } else {
 #pragma unroll
               for (int r = 0; r < 4; ++r) {
@@ -286,7 +319,7 @@ __device__ __forceinline__ void layer(const DenseBatchWArgs& a, const Tile& T, i
         }
       }
     }
-    if (last) {   // uniform: the row's squared error and argmaxes over the wave's units
+    if (last && !head) {   // uniform: the row's squared error and argmaxes over the wave's units
       se += xor16(se, lane);
       se += xor32(se, lane);
       take_max(by, iy, xor16(by, lane), xor16i(iy, lane));
@@ -326,7 +359,13 @@ __device__ __forceinline__ void layer(const DenseBatchWArgs& a, const Tile& T, i
   }
   if (pen && !bwd) lpen += (double)(l1 * s1 + l2 * s2);
   __syncthreads();
-  if (last && tid < T.live) {   // waves in order
+  if (head && tid < T.live) {   // the row's thread: cross-entropy and argmax match
+    const DenseHeadRow hr = head_merge(T.s_part, R, tid);
+    const int64_t pos = T.pos0 + tid;
+    lsum += (double)head_loss(hr);
+    lcnt += hr.arg == a.labels[a.order ? (int64_t)a.order[pos] : pos] ? 1.0 : 0.0;
+  }
+  if (last && !head && tid < T.live) {   // waves in order
     float se = 0.f, by = -INFINITY, bt = -INFINITY;
     int iy = INT_MAX, it = INT_MAX;
     for (int w = 0; w < NWV; ++w) {
@@ -341,14 +380,17 @@ __device__ __forceinline__ void layer(const DenseBatchWArgs& a, const Tile& T, i
   copy_out(a, T, is_dz ? Po.dz : a.P.L[l + 1].h, Po.dw, tid);
 }
 
+template <bool HEAD>
 __device__ __forceinline__ void run_layer(const DenseBatchWArgs& a, const Tile& T, int l, bool bwd, int tid, double& lsum,
                                           double& lcnt, double& lpen) {
   const int nub = ((bwd ? a.L[l].in : a.L[l].units) + 15) >> 4;
-  if (nub <= NWV) layer<1>(a, T, l, bwd, tid, lsum, lcnt, lpen);
-  else if (nub <= 2 * NWV) layer<2>(a, T, l, bwd, tid, lsum, lcnt, lpen);
-  else layer<4>(a, T, l, bwd, tid, lsum, lcnt, lpen);
+  if (nub <= NWV) layer<1, HEAD>(a, T, l, bwd, tid, lsum, lcnt, lpen);
+  else if (nub <= 2 * NWV) layer<2, HEAD>(a, T, l, bwd, tid, lsum, lcnt, lpen);
+  else layer<4, HEAD>(a, T, l, bwd, tid, lsum, lcnt, lpen);
 }
 
+// HEAD: the instance for a.head == DBW_HEAD_SOFTMAX; the other one is untouched by the head
+template <bool HEAD>
 __global__ __launch_bounds__(NTHR) void dense_batchw_fb_kernel(const DenseBatchWArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   __shared__ double s_red[NTHR];
@@ -388,9 +430,9 @@ __global__ __launch_bounds__(NTHR) void dense_batchw_fb_kernel(const DenseBatchW
     __syncthreads();
     copy_out(a, T, a.P.L[0].h, a.P.L[0].hw, tid);
 #pragma unroll 1
-    for (int l = 0; l < a.nl; ++l) run_layer(a, T, l, false, tid, lsum, lcnt, lpen);
+    for (int l = 0; l < a.nl; ++l) run_layer<HEAD>(a, T, l, false, tid, lsum, lcnt, lpen);
 #pragma unroll 1
-    for (int l = a.nl - 1; l >= 1; --l) run_layer(a, T, l, true, tid, lsum, lcnt, lpen);
+    for (int l = a.nl - 1; l >= 1; --l) run_layer<HEAD>(a, T, l, true, tid, lsum, lcnt, lpen);
   }
   __syncthreads();
   for (int i = tid; i < a.P.ndb; i += NTHR) a.dbp[(int64_t)grp * a.P.ndb + i] = T.s_db[i];
@@ -405,7 +447,8 @@ __global__ __launch_bounds__(NTHR) void dense_batchw_fb_kernel(const DenseBatchW
     __syncthreads();
   }
   if (tid == 0) {
-    a.wpairs[2 * grp] = (float)(tot[0] / ((double)a.batch * (double)O) + tot[2] / (double)a.batch);
+    const double rows = (double)a.batch;   // a head's loss is a mean over rows, the squared error's over rows and units
+    a.wpairs[2 * grp] = (float)(tot[0] / (HEAD ? rows : rows * (double)O) + tot[2] / rows);
     a.wpairs[2 * grp + 1] = (float)tot[1];
   }
 }
@@ -524,7 +567,7 @@ __global__ __launch_bounds__(DBW_WTHREADS) void dense_batchw_wgrad_kernel(const 
     }
 }
 
-DenseFwdLdsMark<1> lds_mark;   // of dense_batchw_fb_kernel
+DenseFwdLdsMark<2> lds_mark;   // of dense_batchw_fb_kernel<no head / head>
 
 }  // namespace
 
@@ -532,7 +575,9 @@ DenseFwdLdsMark<1> lds_mark;   // of dense_batchw_fb_kernel
 // comes another way.
 hipError_t dense_batchw_launch(const DenseBatchWArgs& a, hipStream_t stream) {
   if (a.nl < 1 || a.nl > DBW_MAXLAYERS) return hipErrorInvalidValue;
-  if (!dense_batchw_check(a.L, a.nl, a.D, a.batch, a.nflat, a.y != nullptr).empty()) return hipErrorInvalidValue;
+  const bool head = a.head != DBW_HEAD_NONE;
+  if ((a.labels != nullptr) != head || (head && a.y)) return hipErrorInvalidValue;
+  if (!dense_batchw_check(a.L, a.nl, a.D, a.batch, a.nflat, a.y != nullptr || head, a.head).empty()) return hipErrorInvalidValue;
   const DenseBatchWPlan P = dense_batchw_plan(a.L, a.nl, a.batch);
   if (P.ws_words != a.P.ws_words || P.img_words != a.P.img_words || P.lds_bytes != a.P.lds_bytes || P.rows != a.P.rows ||
       a.row0 < 0 || a.row0 + a.batch > a.n || a.G < 1 || a.G > dense_batchw_tiles(a.batch) || a.S < 1 ||
@@ -541,11 +586,11 @@ hipError_t dense_batchw_launch(const DenseBatchWArgs& a, hipStream_t stream) {
       (reinterpret_cast<uintptr_t>(a.ws) & 15) || (reinterpret_cast<uintptr_t>(a.slots) & 15) || !a.items || !a.slab ||
       !a.pairs || !a.dbp || !a.wpairs)
     return hipErrorInvalidValue;
-  const void* fn = reinterpret_cast<const void*>(dense_batchw_fb_kernel);
-  const hipError_t e = lds_mark.ensure(fn, 0, P.lds_bytes);
+  void (*const fb)(const DenseBatchWArgs) = head ? dense_batchw_fb_kernel<true> : dense_batchw_fb_kernel<false>;
+  const hipError_t e = lds_mark.ensure(reinterpret_cast<const void*>(fb), head ? 1 : 0, P.lds_bytes);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(dense_batchw_image_kernel, dim3((P.img_words / 8 + IMG_NT - 1) / IMG_NT), dim3(IMG_NT), 0, stream, a);
-  hipLaunchKernelGGL(dense_batchw_fb_kernel, dim3(a.G), dim3(NTHR), (size_t)P.lds_bytes, stream, a);
+  hipLaunchKernelGGL(fb, dim3(a.G), dim3(NTHR), (size_t)P.lds_bytes, stream, a);
   hipLaunchKernelGGL(dense_batchw_wgrad_kernel, dim3(a.nitems), dim3(DBW_WTHREADS), 0, stream, a);
   return hipGetLastError();
 }

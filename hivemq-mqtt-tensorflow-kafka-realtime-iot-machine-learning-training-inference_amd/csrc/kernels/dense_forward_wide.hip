@@ -40,12 +40,21 @@
 // (over the activation tile, which is free by then), folded in wave order by the row's thread.  sums:
 // every thread adds its rows in doubles, thread 0 folds the workgroup's in index order; no atomics.
 //
+// SOFTMAX HEAD (a.head = 1: the kernel's HEAD instances, one per tile size; sml_dense_head.h).  The last
+// layer is linear in the table; its logits go through the train step's online-softmax merge: per wave and
+// row (max, argmax, sum exp(z - max), the label's logit) into the partials, one barrier, then every lane
+// merges the eight partials of its rows in wave order.  rec takes the probabilities exp(z - M) / S from
+// the accumulators, sums the per-workgroup [sum of log S + M - z_label, rows whose argmax is the label]
+// against a.labels (int32 [n]).  Scores and flags are refused with a head.  157 / 233 VGPRs at RT = 4 / 8
+// (153 / 229 without a head, as before), no scratch.
+//
 // A ROW'S BITS depend on the row and the weights only: the k order of a unit is kb ascending whatever
 // RT, the grid or the row's place in the tile, and the fold over lanes and waves is fixed.
 #include <climits>
 
 #include "sml_common.h"
 #include "sml_dense_fwd_launch.h"
+#include "sml_dense_head.h"
 #include "sml_ops.h"
 
 namespace sml {
@@ -64,18 +73,10 @@ __device__ __forceinline__ int opaque(int v) {
   return v;
 }
 
-// (value, index) of the larger, the lower index on a tie
-__device__ __forceinline__ void take_max(float& b, int& i, float ob, int oi) {
-  if (ob > b || (ob == b && oi < i)) {
-    b = ob;
-    i = oi;
-  }
-}
-
 // One layer over the tile, for a layer whose waves own up to UBN unit blocks (ub = wid + 8 j).  The
 // MFMA loop has no branch: a block past nub runs on block nub - 1's fragments (the loads stay inside
 // the image) and is never written.  The last layer ends in the epilogue.
-template <int RT, int UBN>
+template <int RT, int UBN, bool HEAD>
 __device__ __forceinline__ void run_layer(const DenseFwdWArgs& a, int l, uint16_t* s_act, int S, int64_t row0, int live,
                                           int tid, double& lsum, double& lcnt) {
   constexpr int R = 16 * RT;
@@ -151,6 +152,41 @@ __device__ __forceinline__ void run_layer(const DenseFwdWArgs& a, int l, uint16_
   const bool norm = a.scale != nullptr;
   const bool want_target = a.score != nullptr || a.sums != nullptr;
   float* const s_part = reinterpret_cast<float*>(s_act);
+  if constexpr (HEAD) {   // softmax over the logits; rec takes the probabilities, sums the cross-entropy
+#pragma unroll
+    for (int t = 0; t < RT; ++t) {
+      const int64_t row = row0 + 16 * t + c;
+      const int lab = a.sums && row < a.n ? a.labels[row] : -1;
+      head_wave_partial<UBN>(acc[t], wid, nub, out, lab, lane, s_part + (wid * R + 16 * t + c) * DFWW_PART_WORDS);
+    }
+    __syncthreads();
+    if (a.rec && wid < nub) {
+#pragma unroll
+      for (int t = 0; t < RT; ++t) {
+        const int64_t row = row0 + 16 * t + c;
+        const DenseHeadRow hr = head_merge(s_part, R, 16 * t + c);
+        float* const rr = a.rec + row * out;
+#pragma unroll
+        for (int j = 0; j < UBN; ++j) {
+          const int ub = wid + NWV * j;
+          if (ub < nub) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+              const int u = 16 * ub + 4 * g + r;
+              if (u < out && row < a.n) rr[u] = head_prob(acc[t][j][r], hr);
+            }
+          }
+        }
+      }
+    }
+    if (a.sums && tid < live) {
+      const DenseHeadRow hr = head_merge(s_part, R, tid);
+      lsum += (double)head_loss(hr);
+      lcnt += hr.arg == a.labels[row0 + tid] ? 1.0 : 0.0;
+    }
+    __syncthreads();   // before the next tile's rows overwrite the partials
+    return;
+  }
 #pragma unroll
   for (int t = 0; t < RT; ++t) {
     const int64_t row = row0 + 16 * t + c;
@@ -229,7 +265,8 @@ __device__ __forceinline__ void run_layer(const DenseFwdWArgs& a, int l, uint16_
   }
 }
 
-template <int RT>
+// HEAD: the instance whose epilogue is the softmax head; the other one is untouched by it
+template <int RT, bool HEAD>
 __global__ __launch_bounds__(NTHR) void dense_fwdw_kernel(DenseFwdWArgs a, int S) {
   constexpr int R = 16 * RT;
   extern __shared__ __attribute__((aligned(16))) uint16_t s_act[];   // [R][S] bf16; the epilogue's partials
@@ -264,9 +301,9 @@ __global__ __launch_bounds__(NTHR) void dense_fwdw_kernel(DenseFwdWArgs a, int S
 #pragma unroll 1
     for (int l = 0; l < a.nl; ++l) {
       const int nub = (a.L[l].out + 15) >> 4;
-      if (nub <= NWV) run_layer<RT, 1>(a, l, s_act, S, row0, live, tid, lsum, lcnt);
-      else if (nub <= 2 * NWV) run_layer<RT, 2>(a, l, s_act, S, row0, live, tid, lsum, lcnt);
-      else run_layer<RT, 4>(a, l, s_act, S, row0, live, tid, lsum, lcnt);
+      if (nub <= NWV) run_layer<RT, 1, HEAD>(a, l, s_act, S, row0, live, tid, lsum, lcnt);
+      else if (nub <= 2 * NWV) run_layer<RT, 2, HEAD>(a, l, s_act, S, row0, live, tid, lsum, lcnt);
+      else run_layer<RT, 4, HEAD>(a, l, s_act, S, row0, live, tid, lsum, lcnt);
     }
   }
   if (a.sums) {
@@ -289,14 +326,16 @@ __global__ __launch_bounds__(NTHR) void dense_fwdw_kernel(DenseFwdWArgs a, int S
 
 std::string args_check(const DenseFwdWArgs& a) {
   if (a.nl < 1 || a.nl > DFW_MAXLAYERS) return dense_fwdw_check(a.L, a.nl, a.D, -1, false);
-  std::string why = dense_fwdw_check(a.L, a.nl, a.D, a.img_words, a.score != nullptr || (a.sums && !a.y));
+  std::string why = dense_fwdw_check(a.L, a.nl, a.D, a.img_words, a.score != nullptr || (a.sums && !a.y && !a.head), a.head);
   if (why.empty()) why = dense_fwd_args_why(a, a.image, a.sums);
   if (!why.empty()) return why;
+  if (a.head ? (a.y || (a.sums != nullptr) != (a.labels != nullptr)) : a.labels != nullptr)
+    return "labels come with a softmax head's sums, and with nothing else";
   if (a.tile != 0 && a.tile != DFWW_ROWS_SMALL && a.tile != DFWW_ROWS_LARGE) return "a tile has 64 or 128 rows";
   return "";
 }
 
-DenseFwdLdsMark<2> lds_mark;   // of dense_fwdw_kernel<4 / 8>
+DenseFwdLdsMark<4> lds_mark;   // of dense_fwdw_kernel<4 / 8, no head / head>
 
 }  // namespace
 
@@ -312,12 +351,12 @@ hipError_t dense_fwdw_launch(const DenseFwdWArgs& a, hipStream_t stream) {
   if (!args_check(a).empty()) return hipErrorInvalidValue;
   const DenseFwdWPlan P = dense_fwdw_plan(a.L, a.nl, dense_fwdw_rows(a.n, dense_fwd_cu_count(), a.tile));
   const int grid = dense_fwdw_grid(a.L, a.nl, a.n, a.max_blocks, a.tile);
-  const bool large = P.rows == DFWW_ROWS_LARGE;
-  const void* fn = large ? reinterpret_cast<const void*>(dense_fwdw_kernel<8>) : reinterpret_cast<const void*>(dense_fwdw_kernel<4>);
-  const hipError_t e = lds_mark.ensure(fn, large ? 1 : 0, P.lds_bytes);
+  const bool large = P.rows == DFWW_ROWS_LARGE, head = a.head != 0;
+  void (*const fn)(DenseFwdWArgs, int) = large ? (head ? dense_fwdw_kernel<8, true> : dense_fwdw_kernel<8, false>)
+                                               : (head ? dense_fwdw_kernel<4, true> : dense_fwdw_kernel<4, false>);
+  const hipError_t e = lds_mark.ensure(reinterpret_cast<const void*>(fn), (large ? 1 : 0) + (head ? 2 : 0), P.lds_bytes);
   if (e != hipSuccess) return e;
-  if (large) hipLaunchKernelGGL(dense_fwdw_kernel<8>, dim3(grid), dim3(NTHR), (size_t)P.lds_bytes, stream, a, P.stride);
-  else hipLaunchKernelGGL(dense_fwdw_kernel<4>, dim3(grid), dim3(NTHR), (size_t)P.lds_bytes, stream, a, P.stride);
+  hipLaunchKernelGGL(fn, dim3(grid), dim3(NTHR), (size_t)P.lds_bytes, stream, a, P.stride);
   return hipGetLastError();
 }
 

@@ -1259,29 +1259,46 @@ c10::optional<at::Tensor> dense_forward(const at::Tensor& x, const at::Tensor& i
 
 // ---- the wide variant (dense_forward_wide.hip, sml_dense_fwdw_plan.h) ----
 // Table rows as dense_fwd_table reads them, with offsets in 16-bit words of the bf16 image.  Empty when dense_forward_wide.hip takes the stack (score: against the input row), else the limit it exceeds.
-std::string dense_fwdw_check(const std::vector<std::vector<int64_t>>& table, int64_t img_words, bool score) {
+std::string dense_fwdw_check(const std::vector<std::vector<int64_t>>& table, int64_t img_words, bool score, int64_t head) {
   sml::DenseFwdLayer L[sml::DFW_MAXLAYERS] = {};
   const int nl = dense_fwd_table(table, L);
-  return sml::dense_fwdw_check(L, nl, nl ? L[0].in : 0, img_words, score);
+  return sml::dense_fwdw_check(L, nl, nl ? L[0].in : 0, img_words, score, (int)std::min<int64_t>(std::max<int64_t>(head, -1), 2));
+}
+
+// int32 [n] classes of a softmax head, on x's device
+static const int32_t* head_labels(const char* who, const at::Tensor& labels, const at::Tensor& x) {
+  TORCH_CHECK(labels.is_cuda() && labels.device() == x.device() && labels.scalar_type() == at::kInt && labels.dim() == 1 &&
+                  labels.numel() == x.size(0) && labels.is_contiguous(),
+              who, ": labels must be a contiguous device int32 [", x.size(0), "] on x's device");
+  return labels.data_ptr<int32_t>();
 }
 
 // dense_forward's arguments and results on the wide kernel: image is the bf16 image as int16 words;
-// tile: 64 or 128 rows per workgroup tile, 0 for the kernel's choice.
+// tile: 64 or 128 rows per workgroup tile, 0 for the kernel's choice.  head = 1: the last layer (linear in
+// the table) goes through softmax: rec takes the probabilities, sums = (cross-entropy sum, rows whose argmax is
+// the label) against labels int32 [n]; scores are refused.
 c10::optional<at::Tensor> dense_forward_wide(const at::Tensor& x, const at::Tensor& image,
                                              const std::vector<std::vector<int64_t>>& table,
                                              const c10::optional<at::Tensor>& scale, const c10::optional<at::Tensor>& shift,
                                              const c10::optional<at::Tensor>& rec, const c10::optional<at::Tensor>& score,
                                              const c10::optional<at::Tensor>& flag, double threshold, bool sums,
-                                             const c10::optional<at::Tensor>& y, int64_t max_blocks, int64_t tile) {
+                                             const c10::optional<at::Tensor>& y, int64_t max_blocks, int64_t tile,
+                                             const c10::optional<at::Tensor>& labels, int64_t head) {
   check_dev(x, "x", at::kFloat);
   check_dev(image, "image", at::kShort);
   TORCH_CHECK(image.dim() == 1 && image.is_contiguous(), "image must be a flat int16 tensor");
   TORCH_CHECK(image.device() == x.device(), "image must live on x's device");
   sml::DenseFwdWArgs a{};
-  const bool scored = score.has_value() || (sums && !y.has_value());
+  TORCH_CHECK(head == 0 || head == 1, "dense_forward_wide: head must be 0 or 1");
+  const bool scored = score.has_value() || (sums && !y.has_value() && !head);
   a.nl = dense_fwd_table(table, a.L);
-  dense_fwd_io(a, "dense_forward_wide", sml::dense_fwdw_check(a.L, a.nl, a.nl ? a.L[0].in : 0, image.numel(), scored), x,
-               scale, shift, rec, score, flag, score.has_value(), sml::DFW_WHY_FLAGS, sums, y, max_blocks);
+  a.head = (int)head;
+  dense_fwd_io(a, "dense_forward_wide",
+               sml::dense_fwdw_check(a.L, a.nl, a.nl ? a.L[0].in : 0, image.numel(), scored, a.head), x, scale, shift, rec,
+               score, flag, score.has_value(), sml::DFW_WHY_FLAGS, sums, y, max_blocks, &labels);
+  TORCH_CHECK(head ? !y.has_value() && labels.has_value() == sums : !labels.has_value(),
+              "dense_forward_wide: labels come with a softmax head's sums, and with nothing else");
+  if (labels.has_value()) a.labels = head_labels("dense_forward_wide", *labels, x);
   TORCH_CHECK(tile == 0 || tile == sml::DFWW_ROWS_SMALL || tile == sml::DFWW_ROWS_LARGE, "tile must be 0, 64 or 128");
   const int64_t n = a.n;
   a.image = reinterpret_cast<const uint16_t*>(image.data_ptr<int16_t>());
@@ -1677,12 +1694,13 @@ std::tuple<at::Tensor, at::Tensor> dense_batch_grad(const at::Tensor& flat, cons
 
 // Empty when dense_batch_wide.hip can run a step of this batch on the stack, else the limit it exceeds.
 std::string dense_batchw_check(const std::vector<std::vector<double>>& table, int64_t batch, int64_t nflat,
-                               bool own_targets) {
+                               bool own_targets, int64_t head) {
   if (table.empty() || table.size() > (size_t)sml::DBW_MAXLAYERS)
     return sml::dense_batchw_check(nullptr, (int)table.size(), 0, batch, nflat, own_targets);
   sml::DenseMBLayer L[sml::DMB_MAXLAYERS] = {};
   const int nl = dense_mb_table(table, L);
-  return sml::dense_batchw_check(L, nl, L[0].in, batch, nflat < 0 ? INT64_MAX : nflat, own_targets);
+  return sml::dense_batchw_check(L, nl, L[0].in, batch, nflat < 0 ? INT64_MAX : nflat, own_targets,
+                                 (int)std::min<int64_t>(std::max<int64_t>(head, -1), 2));
 }
 
 // What dense_batchw_train and dense_batchw_grad share: the checks, the launch arguments, the buffers
@@ -1721,15 +1739,23 @@ struct DenseBatchWCall {
 
   DenseBatchWCall(const char* who, const at::Tensor& flat, const std::vector<std::vector<double>>& table,
                   const at::Tensor& x, const c10::optional<at::Tensor>& y, const c10::optional<at::Tensor>& order,
-                  int64_t row0, int64_t batch_, int64_t groups_, int64_t splits_) {
+                  int64_t row0, int64_t batch_, int64_t groups_, int64_t splits_, const c10::optional<at::Tensor>& labels,
+                  int64_t head) {
     check_dev(flat, "flat", at::kFloat);
     check_dev(x, "x", at::kFloat);
     TORCH_CHECK(flat.is_contiguous() && flat.numel() % 4 == 0 && flat.numel() < (1 << 30) &&
                     reinterpret_cast<uintptr_t>(flat.data_ptr<float>()) % 16 == 0,
                 who, ": flat must be contiguous, 16-byte aligned and a multiple of 4 floats long");
     const sml::DenseMBArgs r = dense_mb_rows({who, "n", "permutation of the n samples"}, table,
-                                             dense_batchw_check(table, batch_, flat.numel(), y.has_value()), x, y, order,
-                                             batch_, sml::DMB_BF16);
+                                             dense_batchw_check(table, batch_, flat.numel(),
+                                                                y.has_value() || labels.has_value(), head),
+                                             x, y, order, batch_, sml::DMB_BF16);
+    TORCH_CHECK(head ? labels.has_value() && !y.has_value() : !labels.has_value(), who,
+                ": a softmax head takes labels and no y; labels come with a head alone");
+    if (head) {
+      g.labels = head_labels(who, *labels, x);
+      g.head = (int)head;
+    }
     const int64_t n = x.size(0);
     TORCH_CHECK(row0 >= 0 && row0 < n, who, ": row0 ", row0, " is outside the ", n, " rows of x");
     TORCH_CHECK(groups_ >= 0 && groups_ < (1 << 30) && splits_ >= 0 && splits_ < (1 << 30), who, ": bad groups ", groups_,
@@ -1788,7 +1814,7 @@ at::Tensor dense_batchw_train(const at::Tensor& flat, const at::Tensor& m, const
                               const std::vector<std::vector<double>>& table, const at::Tensor& x,
                               const c10::optional<at::Tensor>& y, const c10::optional<at::Tensor>& order, int64_t row0,
                               int64_t batch, int64_t nsteps, double lr, double beta1, double beta2, double eps,
-                              int64_t groups, int64_t splits) {
+                              int64_t groups, int64_t splits, const c10::optional<at::Tensor>& labels, int64_t head) {
   check_dev(m, "m", at::kFloat);
   check_dev(v, "v", at::kFloat);
   TORCH_CHECK(iter.is_cuda() && iter.scalar_type() == at::kLong && iter.numel() == 1, "iter must be a device int64[1]");
@@ -1797,7 +1823,7 @@ at::Tensor dense_batchw_train(const at::Tensor& flat, const at::Tensor& m, const
   TORCH_CHECK(nsteps >= 1 && nsteps < (1 << 30), "bad nsteps");
   check_dev(x, "x", at::kFloat);
   c10::hip::HIPGuard guard(x.device().index());
-  DenseBatchWCall call("dense_batchw_train", flat, table, x, y, order, row0, batch, groups, splits);
+  DenseBatchWCall call("dense_batchw_train", flat, table, x, y, order, row0, batch, groups, splits, labels, head);
   auto out = at::zeros({nsteps, 2}, flat.options());
   const at::Tensor iter0 = iter.clone();   // the count before the first step: no launch writes it
   call.ap.flat = flat.data_ptr<float>();
@@ -1823,10 +1849,11 @@ at::Tensor dense_batchw_train(const at::Tensor& flat, const at::Tensor& m, const
 std::tuple<at::Tensor, at::Tensor> dense_batchw_grad(const at::Tensor& flat, const std::vector<std::vector<double>>& table,
                                                      const at::Tensor& x, const c10::optional<at::Tensor>& y,
                                                      const c10::optional<at::Tensor>& order, int64_t row0, int64_t batch,
-                                                     int64_t groups, int64_t splits) {
+                                                     int64_t groups, int64_t splits,
+                                                     const c10::optional<at::Tensor>& labels, int64_t head) {
   check_dev(x, "x", at::kFloat);
   c10::hip::HIPGuard guard(x.device().index());
-  DenseBatchWCall call("dense_batchw_grad", flat, table, x, y, order, row0, batch, groups, splits);
+  DenseBatchWCall call("dense_batchw_grad", flat, table, x, y, order, row0, batch, groups, splits, labels, head);
   auto grad = at::zeros({flat.numel()}, flat.options());
   auto out = at::zeros({2}, flat.options());
   call.ap.grad_out = grad.data_ptr<float>();
@@ -2495,18 +2522,21 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("dense_batchw_train", &dense_batchw_train,
         "wide large-batch trainer: nsteps Keras Adam steps of a Dense stack up to 512 wide (dense_mb_train's table), "
         "four launches per step on bf16 MFMAs; groups: forward / backward workgroups of a step (0: one per CU); "
-        "splits: row splits of the weight gradients (0: the kernel's choice)",
+        "splits: row splits of the weight gradients (0: the kernel's choice); head = 1 with labels int32 [n] and no y: "
+        "softmax + sparse categorical cross-entropy over the last layer, which is linear in the table",
         py::arg("flat"), py::arg("m"), py::arg("v"), py::arg("iter"), py::arg("table"), py::arg("x"),
         py::arg("y") = py::none(), py::arg("order") = py::none(), py::arg("row0") = 0, py::arg("batch") = 1024,
         py::arg("nsteps") = 1, py::arg("lr") = 1e-3, py::arg("beta1") = 0.9, py::arg("beta2") = 0.999,
-        py::arg("eps") = 1e-7, py::arg("groups") = 0, py::arg("splits") = 0);
+        py::arg("eps") = 1e-7, py::arg("groups") = 0, py::arg("splits") = 0, py::arg("labels") = py::none(),
+        py::arg("head") = 0);
   m.def("dense_batchw_grad", &dense_batchw_grad,
         "one step of dense_batchw_train without the update -> (summed gradient [nflat], [mean loss, correct rows])",
         py::arg("flat"), py::arg("table"), py::arg("x"), py::arg("y") = py::none(), py::arg("order") = py::none(),
-        py::arg("row0") = 0, py::arg("batch") = 1024, py::arg("groups") = 0, py::arg("splits") = 0);
+        py::arg("row0") = 0, py::arg("batch") = 1024, py::arg("groups") = 0, py::arg("splits") = 0,
+        py::arg("labels") = py::none(), py::arg("head") = 0);
   m.def("dense_batchw_check", &dense_batchw_check,
         "empty if dense_batchw_train can run the table at this batch, else the reason", py::arg("table"),
-        py::arg("batch"), py::arg("nflat") = -1, py::arg("own_targets") = false);
+        py::arg("batch"), py::arg("nflat") = -1, py::arg("own_targets") = false, py::arg("head") = 0);
   m.def("dense_mb_train_fleet", &dense_mb_train_fleet,
         "one launch for M Dense stacks of one architecture, one workgroup per model: flat / m / v [M, stride], iter [M], "
         "host descriptors models [M, 4] int64 and schedule sched [M] int32 -> [M, max nsteps, 2]",
@@ -2526,15 +2556,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("table"), py::arg("img_floats") = -1, py::arg("score") = false);
   m.def("dense_forward_wide", &dense_forward_wide,
         "dense_forward for stacks up to 512 wide on bf16 MFMAs: image is the bf16 image as int16 words (table offsets "
-        "in words); tile = rows of a workgroup's tile (64, 128, or 0 for the kernel's choice)",
+        "in words); tile = rows of a workgroup's tile (64, 128, or 0 for the kernel's choice); head = 1: softmax over "
+        "the last (linear) layer, rec = probabilities, sums = (cross-entropy sum, correct rows) against labels int32 [n]",
         py::arg("x"), py::arg("image"), py::arg("table"), py::arg("scale") = py::none(), py::arg("shift") = py::none(),
         py::arg("rec") = py::none(), py::arg("score") = py::none(), py::arg("flag") = py::none(),
         py::arg("threshold") = 0.0, py::arg("sums") = false, py::arg("y") = py::none(), py::arg("max_blocks") = 0,
-        py::arg("tile") = 0);
+        py::arg("tile") = 0, py::arg("labels") = py::none(), py::arg("head") = 0);
   m.def("dense_fwdw_check", &dense_fwdw_check,
         "empty if dense_forward_wide takes the table (img_words < 0: offsets unchecked; score: against the input row), "
         "else the limit it exceeds",
-        py::arg("table"), py::arg("img_words") = -1, py::arg("score") = false);
+        py::arg("table"), py::arg("img_words") = -1, py::arg("score") = false, py::arg("head") = 0);
   m.attr("DFWW_MAXLAYERS") = (int)sml::DFWW_MAXLAYERS;
   m.attr("DFWW_MAXW") = (int)sml::DFWW_MAXW;
   m.def("dense_forward_fleet", &dense_forward_fleet,

@@ -430,7 +430,10 @@ class Model:
         a limit of the stack, no ROCm device, several ranks, a ``Stream`` input, or the recognised
         autoencoder, which has a throughput engine of its own; ``"auto"`` never picks it.
         ``"wide"`` is the same step for stacks up to 512 wide (``ops.dense_batch_wide``: four
-        launches per step, weights streamed from L2), under the same rules."""
+        launches per step, weights streamed from L2), under the same rules.  It is also the one fused
+        engine that trains a classifier: a last ``Dense(n, "softmax")`` under
+        ``sparse_categorical_crossentropy`` with integer labels ``y`` [n] or [n, 1] (classes outside
+        ``[0, n)`` are a ``ValueError``); every other engine but ``"layers"`` refuses such a model."""
         if engine not in ("auto", "persistent", "layers", "throughput", "wide"):
             raise ValueError(f"engine must be 'auto', 'persistent', 'layers', 'throughput' or 'wide', not {engine!r}")
         if not self.compiled:
@@ -554,7 +557,15 @@ class Model:
             xs = x if isinstance(x, torch.Tensor) else np.asarray(x)
             if xs.ndim != 2 or xs.shape[1] != int(self._input_shape()[0]) or len(xs) == 0:
                 return f"x of shape {tuple(xs.shape)} is not [n, {int(self._input_shape()[0])}] rows"
-            if own_targets:
+            if own_targets and throughput == "wide" and dense_batch_wide.has_head(self):
+                ys = y if isinstance(y, torch.Tensor) else np.asarray(y)
+                units = int(self.output_shape[-1])
+                if len(ys) != len(xs) or ys.ndim > 2 or (ys.ndim == 2 and ys.shape[1] != 1):
+                    return f"labels of shape {tuple(ys.shape)} are not [{len(xs)}] or [{len(xs)}, 1] classes"
+                lo, hi = (int(v) for v in (torch.aminmax(ys) if isinstance(ys, torch.Tensor) else (ys.min(), ys.max())))
+                if lo < 0 or hi >= units:   # the one read of the labels before the first launch
+                    return f"labels span {lo}..{hi}: the softmax head has classes 0..{units - 1}"
+            elif own_targets:
                 ys = y if isinstance(y, torch.Tensor) else np.asarray(y)
                 if ys.ndim != 2 or ys.shape[1] != int(self.output_shape[-1]) or len(ys) != len(xs):
                     return f"y of shape {tuple(ys.shape)} is not [{len(xs)}, {int(self.output_shape[-1])}] rows"
@@ -581,7 +592,9 @@ class Model:
         self.last_fit_precision = prec
         if not stream:
             xd = self._prep_x(x).float()
-            yd = None if (y is None or y is x) else self._prep_y(y).float()
+            yd = None if (y is None or y is x) else self._prep_y(y)
+            if yd is not None:   # a softmax head's classes: int32 once per fit
+                yd = yd.reshape(-1).int() if throughput == "wide" and dense_batch_wide.has_head(self) else yd.float()
             n = int(xd.shape[0])
         hist = History()
         cbs = [hist] + list(callbacks or [])
@@ -661,13 +674,22 @@ class Model:
         return hist
 
     # ------------------------------------------------------------------ inference
+    def _wide_head(self, engine: str, evaluate: bool = False) -> bool:
+        """``engine="wide"`` runs this model's final softmax layer as the kernel's head (``evaluate``: and
+        the loss is the head's sparse_categorical_crossentropy)."""
+        return engine == "wide" and self._fused is None and self._head_is_softmax() and (
+            not evaluate or self.loss == "sparse_categorical_crossentropy")
+
     def _bulk_engine(self, what: str, engine: str, x, score: bool = False, need_mse: bool = False):
         """The fused bulk forward that takes this call, or None for the layer loop: ``ops.dense_forward``
         (the whole stack in one launch, fp32, widths up to 128) or, under ``engine="wide"`` alone,
         ``ops.dense_forward_wide`` (bf16 MFMAs with the bf16 trainers' rounding points, widths up to 512).
         ``auto`` takes the fp32 kernel when the device is ROCm, the stack is inside its limits and the rows
         are fp32 (arrays, tensors or a ``Stream``); it never picks ``"wide"``.  ``engine="fused"`` and
-        ``engine="wide"`` raise ``ValueError`` with the reason when they cannot run."""
+        ``engine="wide"`` raise ``ValueError`` with the reason when they cannot run.  Under ``"wide"`` a
+        final softmax layer is the kernel's head (``_wide_head``): ``predict`` gives probabilities, and
+        ``evaluate`` of a sparse_categorical_crossentropy model the mean cross-entropy and accuracy
+        (``need_mse`` is waived for that pair alone); scores with a head are refused."""
         if engine not in ("auto", "fused", "layers", "wide"):
             raise ValueError(f"engine must be 'auto', 'fused', 'layers' or 'wide', not {engine!r}")
         if engine == "layers":
@@ -682,10 +704,11 @@ class Model:
             why = f"the model is on {self.device}, not on a ROCm device"
         elif self._fused is not None:
             why = "the model runs on the fused autoencoder kernels"
-        elif need_mse and self.loss != "mean_squared_error":
+        elif need_mse and self.loss != "mean_squared_error" and not self._wide_head(engine, evaluate=True):
             why = f"loss {self.loss!r}: the kernel sums mean_squared_error"
         else:
-            ok, why = dfw.supports(self, score=score)
+            head = self._wide_head(engine, evaluate=need_mse)
+            ok, why = dfw.supports(self, score=score, head=True) if head else dfw.supports(self, score=score)
             if ok and not isinstance(x, Stream):
                 dt = x.dtype if isinstance(x, torch.Tensor) else np.asarray(x).dtype
                 if dt not in (torch.float32, np.dtype(np.float32)):
@@ -731,16 +754,17 @@ class Model:
             cb.set_model(self)
         outs = []
         dfw = self._bulk_engine("predict", engine, x)
+        kw = {"head": True} if self._wide_head(engine) else {}
         if dfw is not None:
             self.last_predict_engine = self._bulk_name(dfw)
             if not cbs and not isinstance(x, Stream):
                 n, chunk = len(x), max(batch_size, 1 << 20)
                 host = np.empty((n, *self.output_shape), np.float32)
                 for s, xb in zip(range(0, n, chunk), self._bulk_chunks(x, chunk)):
-                    torch.from_numpy(host[s:s + chunk]).copy_(dfw.forward(self, self._bulk_rows(xb))[0])
+                    torch.from_numpy(host[s:s + chunk]).copy_(dfw.forward(self, self._bulk_rows(xb), **kw)[0])
                 return host
             for bi, xb in enumerate(self._bulk_chunks(x, batch_size)):
-                out = dfw.forward(self, self._bulk_rows(xb))[0].cpu().numpy()
+                out = dfw.forward(self, self._bulk_rows(xb), **kw)[0].cpu().numpy()
                 for cb in cbs:
                     cb.on_predict_batch_end(bi, {"outputs": out})
                 outs.append(out)
@@ -760,7 +784,8 @@ class Model:
     @torch.no_grad()
     def evaluate(self, x, y=None, batch_size: int = 1024, verbose: int = 0, engine: str = "auto") -> Tuple[float, float]:
         """(loss, accuracy).  On the fused path (``engine``, ``last_evaluate_engine``: as ``predict``; the
-        loss must be mean_squared_error) the whole array is one launch and one host read.  A model compiled
+        loss must be mean_squared_error, or under ``"wide"`` sparse_categorical_crossentropy on a softmax
+        head with integer labels ``y``) the whole array is one launch and one host read.  A model compiled
         onto the fused autoencoder kernels keeps that path whatever ``engine`` says (``"fused"`` raises)."""
         if not self.compiled:
             self.compile()
@@ -770,6 +795,13 @@ class Model:
         xs = np.asarray(x) if not isinstance(x, torch.Tensor) else x
         ys = xs if y is None else (np.asarray(y) if not isinstance(y, torch.Tensor) else y)
         dfw = self._bulk_engine("evaluate", engine, xs, score=y is None, need_mse=True)
+        if dfw is not None and self._wide_head(engine, evaluate=True):
+            xd, n = self._bulk_rows(xs), max(len(xs), 1)
+            if y is None or len(ys) != len(xd) or np.prod(ys.shape) != len(xd):
+                raise ValueError(f"evaluate(engine='wide'): a softmax head takes y as [{len(xd)}] or [{len(xd)}, 1] classes")
+            self.last_evaluate_engine = "wide"
+            loss, corr = dfw.evaluate_sums(self, xd, labels=self._prep_y(ys).reshape(-1))
+            return loss / n, corr / n
         if dfw is not None:
             xd = self._bulk_rows(xs)
             yd = None if y is None else self._bulk_rows(ys)

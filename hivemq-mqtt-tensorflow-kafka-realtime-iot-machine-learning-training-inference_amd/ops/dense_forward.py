@@ -285,8 +285,12 @@ def _forward(v, supports_, image_, model, x, rec, score, threshold, normalizer, 
 
 
 def _evaluate_sums(v, supports_, image_, model, x, y, normalizer, *tail) -> Tuple[float, float]:
-    part = _launch(v, supports_, image_, model, x, y is None, normalizer, lambda n, out_w: (None, None, None, 0.0, True, y),
-                   tail)[1]
+    return _sum_parts(_launch(v, supports_, image_, model, x, y is None, normalizer,
+                              lambda n, out_w: (None, None, None, 0.0, True, y), tail)[1])
+
+
+def _sum_parts(part) -> Tuple[float, float]:
+    """The per-workgroup pairs a sums launch returned (None: no rows), added in index order: one host read."""
     if part is None:
         return 0.0, 0.0
     tot = np.cumsum(part.cpu().numpy(), axis=0)[-1]   # sequential: index order

@@ -12,6 +12,12 @@ activations stay in LDS.  ``forward`` and ``evaluate_sums`` return what ``ops.de
 of the image, the LDS plan and ``tile``.  The check's rules, ``supports``, the fragment order, the cached
 state and the drivers of ``forward`` / ``evaluate_sums`` are ``ops/dense_forward.py``'s, over ``WIDE``.
 
+The softmax head.  ``head=True`` (``nn.Model.predict / evaluate(engine="wide")`` of a classifier) makes a
+final softmax layer the kernel's head: it enters the table as linear, ``forward`` returns the probabilities
+and ``evaluate_sums(labels=...)`` the cross-entropy sum and the rows whose argmax is the label.  Scores are
+refused with a head, and without ``head`` a softmax layer is refused as before; ``dense_forward.ACT`` has
+no softmax, so the narrow forward, the fleets and the scorers keep refusing it.
+
 The image.  ``pack_image`` is the layout, in numpy (``uint16`` words).  For an ``nn.Model`` the VALUES are
 never cached (kernels update ``model.fp.flat`` in place where no Python hook sees it): what is cached on
 the model is the image's gather index into the flat buffer, and ``image`` is one device gather, one
@@ -52,17 +58,30 @@ def plan(widths, rows: int = 64) -> dict:
     return {"rows": rows, "stride": stride, "lds_bytes": max(rows * stride * 2, WAVES * rows * _PART_WORDS * 4)}
 
 
-def check_shape(widths, activations, score: bool = False) -> str:
+WHY_HEAD_SCORE = "scores need a reconstruction, not a softmax head"
+
+
+def check_shape(widths, activations, score: bool = False, head: bool = False) -> str:
     """Empty if the kernel takes a stack ``widths[0] -> widths[1] -> ...`` with these activation names
-    (``score``: against the input row), else the limit it exceeds -- ``dense_fwdw_check``'s words.  The LDS
-    plan fits at every width inside the limit."""
-    return dfw._check_rows(WIDE, widths, activations, score)
+    (``score``: against the input row; ``head``: the last one is the softmax head), else the limit it
+    exceeds -- ``dense_fwdw_check``'s words.  The LDS plan fits at every width inside the limit."""
+    if not head:
+        return dfw._check_rows(WIDE, widths, activations, score)
+    if score:
+        return WHY_HEAD_SCORE
+    activations = list(activations)
+    if not activations or activations[-1] != "softmax":
+        return "a softmax head needs a final softmax layer"
+    why = dfw._check_rows(WIDE, widths, activations[:-1] + ["linear"], False)
+    if not why and widths[-1] < 2:
+        why = f"a softmax head needs 2..{MAX_WIDTH} units in the last layer and a linear last entry in the table"
+    return why
 
 
-def supports(model, score: bool = False) -> Tuple[bool, str]:
-    """(True, "") if the kernel can run ``model`` (``score``: with scores against the input row), else
-    (False, the limit it exceeds).  Needs no device."""
-    return dfw._supports(lambda: dfw._layers(model, WIDE), lambda w, a: check_shape(w, a, score))
+def supports(model, score: bool = False, head: bool = False) -> Tuple[bool, str]:
+    """(True, "") if the kernel can run ``model`` (``score``: with scores against the input row; ``head``:
+    with its final softmax layer as the head), else (False, the limit it exceeds).  Needs no device."""
+    return dfw._supports(lambda: dfw._layers(model, WIDE), lambda w, a: check_shape(w, a, score, head))
 
 
 def to_bf16(a) -> np.ndarray:
@@ -99,19 +118,42 @@ def image(model) -> Tuple[torch.Tensor, list]:
     return torch.cat(parts), st["table"]
 
 
+def _head_image(model) -> Tuple[torch.Tensor, list]:
+    """``image`` with the final softmax layer linear in the table (a copy: the cached table keeps -1)."""
+    img, table = image(model)
+    return img, [list(t) for t in table[:-1]] + [list(table[-1][:2]) + [ACT["linear"]] + list(table[-1][3:])]
+
+
+def _head_supports(model, score: bool = False) -> Tuple[bool, str]:
+    return supports(model, score=score, head=True)
+
+
 def forward(model, x: torch.Tensor, rec: bool = True, score: bool = False, threshold: Optional[float] = None,
-            normalizer=None, max_blocks: int = 0, tile: int = 0):
+            normalizer=None, max_blocks: int = 0, tile: int = 0, head: bool = False):
     """The stack over device rows ``x`` [n, D] fp32 (any row stride) in one launch.  Returns
     ``(reconstructions [n, out] | None, scores [n] | None, flags [n] bool | None)`` as device tensors;
     flags (``score > threshold``) come with ``score`` and a threshold.  ``tile``: rows of a workgroup's
-    tile (64 or 128; 0: 128 when that still fills every CU).  A model outside the kernel's limits is a
-    ``ValueError``: this function never falls back."""
+    tile (64 or 128; 0: 128 when that still fills every CU).  ``head``: the final softmax layer is the
+    kernel's head and the reconstructions are its probabilities; scores are refused then.  A model outside
+    the kernel's limits is a ``ValueError``: this function never falls back."""
+    if head:
+        return dfw._forward(WIDE, _head_supports, _head_image, model, x, rec, score, threshold, normalizer, int(max_blocks),
+                            int(tile), None, 1)
     return dfw._forward(WIDE, supports, image, model, x, rec, score, threshold, normalizer, int(max_blocks), int(tile))
 
 
 def evaluate_sums(model, x: torch.Tensor, y: Optional[torch.Tensor] = None, normalizer=None,
-                  max_blocks: int = 0, tile: int = 0) -> Tuple[float, float]:
+                  max_blocks: int = 0, tile: int = 0, labels: Optional[torch.Tensor] = None) -> Tuple[float, float]:
     """(sum over rows of the row's mean squared error, rows whose argmax matches the target's) over device
     rows ``x`` against ``y`` [n, out] (or, without ``y``, the normalised row): one launch, one host read,
-    the per-workgroup partials added in index order."""
-    return dfw._evaluate_sums(WIDE, supports, image, model, x, y, normalizer, int(max_blocks), int(tile))
+    the per-workgroup partials added in index order.  ``labels`` (integers, [n] or [n, 1], instead of
+    ``y``): the final softmax layer is the head, and the sums are (cross-entropy, rows whose argmax is the
+    label)."""
+    if labels is None:
+        return dfw._evaluate_sums(WIDE, supports, image, model, x, y, normalizer, int(max_blocks), int(tile))
+    if y is not None or labels.is_floating_point() or labels.numel() != x.shape[0]:
+        raise ValueError(f"wide fused Dense forward: a softmax head takes integer labels [{x.shape[0]}] and no y")
+    lab = labels.reshape(-1).to(device=x.device, dtype=torch.int32).contiguous()
+    part = dfw._launch(WIDE, _head_supports, _head_image, model, x, False, normalizer,
+                       lambda n, out_w: (None, None, None, 0.0, True, None), (int(max_blocks), int(tile), lab, 1))[1]
+    return dfw._sum_parts(part)

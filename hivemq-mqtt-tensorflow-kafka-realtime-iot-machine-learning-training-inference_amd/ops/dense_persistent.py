@@ -167,8 +167,10 @@ def supports(model, batch_size: int = 32, own_targets: bool = False, precision: 
     return (not why), why
 
 
-def table(model) -> List[Tuple[float, ...]]:
-    """Rows (in, units, act, has_bias, l1, l2, w_off, b_off) of the built model's Dense layers."""
+def table(model, head: bool = False) -> List[Tuple[float, ...]]:
+    """Rows (in, units, act, has_bias, l1, l2, w_off, b_off) of the built model's Dense layers.
+    ``head`` (``ops.dense_batch_wide`` alone): a final softmax layer enters as linear, its softmax being
+    the kernel's loss head; every trainer without a head refuses softmax in ``supports``."""
     layers, why = dense_layers(model)
     if layers is None:
         raise ValueError(why)
@@ -179,7 +181,8 @@ def table(model) -> List[Tuple[float, ...]]:
         r = lyr.activity_regularizer
         w_off = int(fp.offsets[lyr.param_slots[0]])
         b_off = int(fp.offsets[lyr.param_slots[1]]) if lyr.use_bias else 0
-        rows.append((width, lyr.units, ACT[lyr.activation], int(bool(lyr.use_bias)), float(r.l1) if r else 0.0,
+        act = ACT["linear"] if head and lyr is layers[-1] and lyr.activation == "softmax" else ACT[lyr.activation]
+        rows.append((width, lyr.units, act, int(bool(lyr.use_bias)), float(r.l1) if r else 0.0,
                      float(r.l2) if r else 0.0, w_off, b_off))
         width = lyr.units
     return rows
