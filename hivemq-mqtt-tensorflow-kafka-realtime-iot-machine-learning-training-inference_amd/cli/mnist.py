@@ -28,6 +28,8 @@ def _flags(p):
     p.add_argument("--no-produce", action="store_true", help="topics xx / yy are already filled")
     p.add_argument("--log-dir", default=None, help="TensorBoard event directory")
     p.add_argument("--save", default=None)
+    p.add_argument("--engine", choices=["layers", "fused", "auto"], default="layers",
+                   help="fused: the two-launch fp32 train step (batch 1..32, one device); auto: where it can run")
 
 
 def main(argv: Sequence[str]) -> int:
@@ -44,7 +46,7 @@ def main(argv: Sequence[str]) -> int:
     if ns.simplified:
         model = MLPClassifier(hidden=512, dropout=0.2, device=ns.device, seed=ns.seed)
         model.fit(xtr, ytr, epochs=ns.epochs, batch_size=32 if ns.batch_size == 1 else ns.batch_size,
-                  validation_data=(xte, yte), callbacks=cbs, verbose=2)
+                  validation_data=(xte, yte), callbacks=cbs, verbose=2, engine=ns.engine)
     else:
         servers = ns.servers or "fake://mnist"
         cfg = common.kafka_config(servers, ns.kafka_config)
@@ -54,7 +56,7 @@ def main(argv: Sequence[str]) -> int:
             print("count(x, y): ", mn.produce_mnist(servers, xtr, ytr, config=cfg), flush=True)
         model = MLPClassifier(hidden=128, device=ns.device, seed=ns.seed)
         model.fit(stream=lambda: mn.kafka_mnist(servers, config=cfg), epochs=ns.epochs, batch_size=ns.batch_size,
-                  steps_per_epoch=ns.steps_per_epoch, callbacks=cbs, verbose=2)
+                  steps_per_epoch=ns.steps_per_epoch, callbacks=cbs, verbose=2, engine=ns.engine)
     loss, acc = model.evaluate(xte, yte)
     print(f"test loss {loss:.4f} accuracy {acc:.4f} ({time.perf_counter() - t0:.1f}s)", flush=True)
     if ns.save:

@@ -11,6 +11,7 @@
 #include "sml_dense_fwdw_plan.h"
 #include "sml_dense_serve_bf16.h"
 #include "sml_dense_mb_plan.h"
+#include "sml_mlp_step.h"
 
 namespace sml {
 
@@ -222,6 +223,30 @@ hipError_t mlp_wgrad_launch(const void* x, int x_u8, int64_t ldx, const float* d
                             hipStream_t st);
 hipError_t mlp_dropout_mask_launch(float* out, int M, int N, float keep, uint32_t seed, uint32_t step,
                                    hipStream_t st);
+
+// ---- fused train step of the MNIST MLP (mlp_step.hip, sml_mlp_step.h): two launches per step ----
+struct MlpStepArgs {
+  float *flat, *m, *v;      // W1 [in][H] | b1 [H] | W2 [H][C] | b2 [C], updated in place
+  int64_t* iter;            // the step count, written by the backward's workgroup 0
+  const int64_t* iter0;     // the count before the call's first step: no launch writes it
+  const void* x;            // [n][ldx] uint8 (scaled by 1/255 as staged) or fp32
+  int x_u8;
+  int64_t ldx;
+  const int64_t* y;         // [n] labels; a label outside [0, C) gives no loss and no gradient
+  const int64_t* order;     // row of sample i is order[i]; nullptr: by position
+  int64_t n, row0;          // the step takes samples row0 .. row0 + batch - 1
+  int batch, in, H, C;
+  float keep, inv_keep;     // Dropout keep probability (1: none)
+  uint32_t seed, step;      // Dropout counter key of this step
+  int s;                    // index of the step within the call
+  float* hbuf;              // [32][mls_ldh(H)] h of the step
+  float* snap;              // [H * C + C] W2 | b2 as the step's forward saw them
+  float* acc;               // [2] += (loss sum, correct rows)
+  float lr, beta1, beta2, eps;
+};
+// `steps` consecutive steps (row0, step and s advance by one step each), 2 * steps launches on `st`;
+// groups: workgroups of the backward (<= 0: mlp_step_groups' default)
+hipError_t mlp_train_steps_launch(MlpStepArgs a, int steps, int groups, hipStream_t st);
 
 // ---- persistent Keras-step trainer for the reference LSTM stack (lstm_ref_train.hip) ----
 int lstm_ref_train_params();

@@ -20,6 +20,7 @@
 // (seed, step, row, column) evaluated in the forward epilogue; the backward needs no
 // mask because H > 0 already implies "kept and active" (H = relu(z) * mask / keep).
 #include "sml_common.h"
+#include "sml_mlp_dropout.h"
 #include "sml_ops.h"
 
 namespace sml {
@@ -30,24 +31,6 @@ constexpr int AS = TK + 1, BS = TN + 1;   // LDS strides (odd: conflict-free)
 
 enum AMode { A_F32 = 0, A_U8 = 1, A_F32_T = 2, A_U8_T = 3 };
 enum Epi { E_STORE = 0, E_BIAS_ACT = 1, E_RELU_MASK = 2 };
-
-__device__ __forceinline__ uint32_t mix32(uint32_t h) {   // murmur3 finaliser
-  h ^= h >> 16;
-  h *= 0x85ebca6bu;
-  h ^= h >> 13;
-  h *= 0xc2b2ae35u;
-  h ^= h >> 16;
-  return h;
-}
-
-// uniform [0, 1) with 24 bits, keyed by (seed, step, row, col)
-__device__ __forceinline__ float dropout_u(uint32_t seed, uint32_t step, uint32_t row, uint32_t col) {
-  uint32_t h = mix32(seed ^ 0x9e3779b9u);
-  h = mix32(h ^ (step * 0x632be5abu));
-  h = mix32(h ^ (row * 0x85157af5u));
-  h = mix32(h ^ col);
-  return (float)(h >> 8) * (1.0f / 16777216.0f);
-}
 
 struct GemmArgs {
   const void* A;

@@ -108,6 +108,7 @@ hipError_t softmax_xent_launch(const float* logits, const int64_t* labels, int64
   if (B <= 0) return hipSuccess;
   switch (C) {
     case 2: return launch_c<2>(logits, labels, B, gscale, dlogits, probs, acc, stream);
+    case 3: return launch_c<3>(logits, labels, B, gscale, dlogits, probs, acc, stream);
     case 10: return launch_c<10>(logits, labels, B, gscale, dlogits, probs, acc, stream);
     case 16: return launch_c<16>(logits, labels, B, gscale, dlogits, probs, acc, stream);
     case 32: return launch_c<32>(logits, labels, B, gscale, dlogits, probs, acc, stream);

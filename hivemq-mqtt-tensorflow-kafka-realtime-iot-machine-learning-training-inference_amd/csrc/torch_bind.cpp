@@ -620,7 +620,7 @@ void softmax_xent(const at::Tensor& logits, const at::Tensor& labels, double gsc
   TORCH_CHECK(logits.dim() == 2 && logits.is_contiguous(), "logits must be contiguous [B, C]");
   const int64_t B = logits.size(0), C = logits.size(1);
   TORCH_CHECK(labels.numel() == B && labels.is_contiguous(), "labels must be [B]");
-  TORCH_CHECK(C == 2 || C == 10 || C == 16 || C == 32, "softmax_xent supports C in {2, 10, 16, 32}");
+  TORCH_CHECK(C == 2 || C == 3 || C == 10 || C == 16 || C == 32, "softmax_xent supports C in {2, 3, 10, 16, 32}");
   for (const auto* t : {&dlogits, &probs}) {
     if (t->has_value()) {
       check_dev(**t, "out", at::kFloat);
@@ -1082,6 +1082,78 @@ at::Tensor mlp_dropout_mask(const at::Tensor& like, int64_t M, int64_t N, double
   SML_CHECK_HIP(sml::mlp_dropout_mask_launch(out.data_ptr<float>(), (int)M, (int)N, (float)keep, (uint32_t)seed,
                                              (uint32_t)step, cur_stream(like)));
   return out;
+}
+
+// Empty when mlp_step.hip can train Flatten -> Dense(hidden, relu) -> [Dropout(rate)] -> Dense(classes,
+// softmax) at this batch, else the limit it exceeds.
+std::string mlp_step_check(int64_t batch, int64_t in, int64_t hidden, int64_t classes, double rate, int64_t world) {
+  return sml::mlp_step_check(batch, in, hidden, classes, rate, world);
+}
+
+// `steps` consecutive Keras steps of the MNIST MLP (mlp_step.hip): 2 * steps launches on the current
+// stream, no host synchronisation.  Step s trains on the samples s * batch .. (s + 1) * batch - 1, sample i
+// being row order[i] of x (row i without order).  flat / m / v / iter are updated in place and acc [2]
+// gains the steps' (loss sum, correct rows).  step0: the Dropout counter of the first step.
+void mlp_train_steps(const at::Tensor& flat, const at::Tensor& m, const at::Tensor& v, const at::Tensor& iter,
+                     const at::Tensor& x, const at::Tensor& y, const c10::optional<at::Tensor>& order,
+                     const at::Tensor& acc, int64_t hidden, int64_t classes, int64_t batch, int64_t steps, double rate,
+                     int64_t seed, int64_t step0, double lr, double beta1, double beta2, double eps, int64_t groups) {
+  check_x_mlp(x);
+  check_dev(flat, "flat", at::kFloat);
+  check_dev(m, "m", at::kFloat);
+  check_dev(v, "v", at::kFloat);
+  check_dev(acc, "acc", at::kFloat);
+  check_dev(y, "y", at::kLong);
+  const int64_t n = x.size(0), in = x.size(1);
+  const std::string why = sml::mlp_step_check(batch, in, hidden, classes, rate, 1);
+  TORCH_CHECK(why.empty(), "mlp_train_steps: ", why);
+  TORCH_CHECK(iter.is_cuda() && iter.scalar_type() == at::kLong && iter.numel() == 1, "iter must be a device int64[1]");
+  TORCH_CHECK(flat.is_contiguous() && m.is_contiguous() && v.is_contiguous() && m.numel() == flat.numel() &&
+                  v.numel() == flat.numel() && flat.numel() >= sml::mls_nparams((int)in, (int)hidden, (int)classes),
+              "flat / m / v must be contiguous, of one size, and hold W1 | b1 | W2 | b2");
+  TORCH_CHECK(acc.is_contiguous() && acc.numel() == 2, "acc must be a contiguous float32 [2]");
+  TORCH_CHECK(y.is_contiguous() && y.numel() == n, "y must be a contiguous int64 [n]");
+  TORCH_CHECK(n >= 1 && n <= INT32_MAX, "x must have 1 .. 2^31 - 1 rows");
+  TORCH_CHECK(steps >= 1 && steps < (1 << 30) && groups >= 0 && groups < (1 << 30), "bad steps / groups");
+  const int64_t samples = steps * batch;
+  if (order.has_value()) {
+    check_dev(*order, "order", at::kLong);
+    TORCH_CHECK(order->is_contiguous() && order->numel() >= samples, "order must be a contiguous int64 [>= steps * batch]");
+  } else {
+    TORCH_CHECK(n >= samples, "x has ", n, " rows, ", steps, " steps of ", batch, " need ", samples);
+  }
+  c10::hip::HIPGuard guard(x.device().index());
+  auto hbuf = at::empty({sml::MLS_MAXBATCH, sml::mls_ldh((int)hidden)}, flat.options());
+  auto snap = at::empty({hidden * classes + classes}, flat.options());
+  const at::Tensor iter0 = iter.clone();   // the count before the first step: no launch writes it
+  sml::MlpStepArgs a{};
+  a.flat = flat.data_ptr<float>();
+  a.m = m.data_ptr<float>();
+  a.v = v.data_ptr<float>();
+  a.iter = iter.data_ptr<int64_t>();
+  a.iter0 = iter0.data_ptr<int64_t>();
+  a.x = x.data_ptr();
+  a.x_u8 = x.scalar_type() == at::kByte;
+  a.ldx = x.stride(0);
+  a.y = y.data_ptr<int64_t>();
+  a.order = order.has_value() ? order->data_ptr<int64_t>() : nullptr;
+  a.n = n;
+  a.batch = (int)batch;
+  a.in = (int)in;
+  a.H = (int)hidden;
+  a.C = (int)classes;
+  a.keep = (float)(1.0 - rate);
+  a.inv_keep = 1.0f / a.keep;
+  a.seed = (uint32_t)seed;
+  a.step = (uint32_t)step0;
+  a.hbuf = hbuf.data_ptr<float>();
+  a.snap = snap.data_ptr<float>();
+  a.acc = acc.data_ptr<float>();
+  a.lr = (float)lr;
+  a.beta1 = (float)beta1;
+  a.beta2 = (float)beta2;
+  a.eps = (float)eps;
+  SML_CHECK_HIP(sml::mlp_train_steps_launch(a, (int)steps, (int)groups, cur_stream(x)));
 }
 
 // N consecutive Keras steps of the reference LSTM stack (look_back 1) in one launch.
@@ -2607,6 +2679,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("out"));
   m.def("mlp_dropout_mask", &mlp_dropout_mask, "the in-kernel dropout multipliers (0 or 1/keep)", py::arg("like"),
         py::arg("M"), py::arg("N"), py::arg("keep"), py::arg("seed"), py::arg("step"));
+  m.def("mlp_step_check", &mlp_step_check, "empty if the fused MLP train step can run, else the limit exceeded",
+        py::arg("batch"), py::arg("in_features"), py::arg("hidden"), py::arg("classes"), py::arg("rate") = 0.0,
+        py::arg("world") = 1);
+  m.def("mlp_train_steps", &mlp_train_steps,
+        "consecutive fused fp32 train steps of Flatten -> Dense(relu) -> [Dropout] -> Dense(softmax), two launches each; "
+        "flat / m / v / iter in place, acc [2] += (loss sum, correct rows)",
+        py::arg("flat"), py::arg("m"), py::arg("v"), py::arg("iter"), py::arg("x"), py::arg("y"), py::arg("order"),
+        py::arg("acc"), py::arg("hidden"), py::arg("classes"), py::arg("batch"), py::arg("steps"), py::arg("rate"),
+        py::arg("seed"), py::arg("step0"), py::arg("lr"), py::arg("beta1"), py::arg("beta2"), py::arg("eps"),
+        py::arg("groups") = 0);
   m.def("lstm_fused_supported", &sml::lstm_fused_supported, "whether (U, IN) has a fused LSTM kernel", py::arg("U"),
         py::arg("IN"));
   py::class_<ServePy>(m, "AEServe", "persistent per-event autoencoder scorer over host-mapped rings")

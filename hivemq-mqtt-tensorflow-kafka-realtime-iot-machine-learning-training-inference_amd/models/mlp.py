@@ -81,6 +81,7 @@ class MLPClassifier:
         self._gen.manual_seed(seed)
         self._seed, self._step = int(seed) & 0xffffffff, 0   # in-kernel dropout RNG key
         self.stop_training = False
+        self.last_fit_engine: Optional[str] = None
 
     # ------------------------------------------------------------------ core
     @property
@@ -193,18 +194,51 @@ class MLPClassifier:
         return float(a[0] / max(n, 1)), float(a[1] / max(n, 1))
 
     # ------------------------------------------------------------------ training
+    def _fused_steps(self, x: torch.Tensor, y: torch.Tensor, order: Optional[torch.Tensor], batch: int,
+                     nb: int) -> Tuple[int, int]:
+        """The first ``nb`` batches of the samples on the fused step: one call for the full batches, one
+        more for a short last batch.  Returns (rows, steps) trained."""
+        from ..ops import mlp_step
+
+        n = len(order) if order is not None else len(x)
+        full = min(nb, n // batch)
+        if full:
+            mlp_step.train_steps(self, x, y, order, batch, full)
+        rows, steps = full * batch, full
+        if full < nb and n > rows:
+            if order is not None:
+                mlp_step.train_steps(self, x, y, order[rows:], n - rows, 1)
+            else:
+                mlp_step.train_steps(self, x[rows:], y[rows:], None, n - rows, 1)
+            rows, steps = n, steps + 1
+        return rows, steps
+
     def fit(self, x=None, y=None, epochs: int = 1, batch_size: int = 32, steps_per_epoch: Optional[int] = None,
             validation_data=None, callbacks: Optional[Sequence[Callback]] = None, shuffle: bool = True,
-            verbose: int = 1, seed: int = 0, stream=None) -> History:
+            verbose: int = 1, seed: int = 0, stream=None, engine: str = "layers") -> History:
         """Arrays (``x`` uint8/float images, ``y`` int labels) or ``stream`` = a callable returning an
         iterator of ``(images, labels)`` chunks (e.g. :func:`streamml.data.mnist.kafka_mnist`), re-read
-        every epoch like a tf.data pipeline."""
+        every epoch like a tf.data pipeline.
+
+        ``engine``: ``"layers"`` trains through :meth:`train_step` (one launch per layer GEMM);
+        ``"fused"`` trains on the two-launch step of :mod:`streamml.ops.mlp_step` (batch 1..32, one
+        device) and raises ``ValueError`` where it cannot; ``"auto"`` takes the fused step where it
+        can.  ``last_fit_engine`` says which ran.  Both draw the same permutations and Dropout masks."""
         import torch.distributed as dist
+        from ..ops import mlp_step
         from ..parallel.dp import allreduce_sum_, shard_range
 
+        if engine not in ("layers", "fused", "auto"):
+            raise ValueError(f"unknown engine {engine!r}: 'layers', 'fused' or 'auto'")
         world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
         rank = dist.get_rank() if world > 1 else 0
         allreduce = allreduce_sum_ if world > 1 else None
+        fused = False
+        if engine != "layers":
+            fused, why = mlp_step.supports(self, batch_size, world=world)
+            if engine == "fused" and not fused:
+                raise ValueError(f"engine='fused': {why}")
+        self.last_fit_engine = "fused" if fused else "layers"
         hist = History()
         cbs = [hist] + list(callbacks or [])
         for cb in cbs:
@@ -218,6 +252,8 @@ class MLPClassifier:
                 xs, ys = xs[s0:s1], ys[s0:s1]
             xd = torch.as_tensor(xs).to(self.device)
             yd = torch.as_tensor(ys.astype(np.int64)).to(self.device)
+            if fused:
+                xd = self._prep(xd)
         rng = np.random.default_rng(seed + rank)
         self.stop_training = False
         for epoch in range(epochs):
@@ -232,6 +268,9 @@ class MLPClassifier:
                 nb = math.ceil(n / batch_size)
                 if steps_per_epoch is not None:
                     nb = min(nb, steps_per_epoch)
+                if fused:
+                    rows, steps = self._fused_steps(xd, yd, order, batch_size, nb)
+                    nb = 0
                 for b in range(nb):
                     idx = order[b * batch_size:(b + 1) * batch_size] if order is not None else \
                         slice(b * batch_size, (b + 1) * batch_size)
@@ -242,6 +281,17 @@ class MLPClassifier:
             else:
                 done = False
                 for cx, cy in stream():
+                    if fused:   # one call per chunk, rows by position
+                        left = None if steps_per_epoch is None else steps_per_epoch - steps
+                        if left == 0:
+                            break
+                        nb = math.ceil(len(cx) / batch_size)
+                        yc = torch.as_tensor(np.asarray(cy).astype(np.int64)).to(self.device).reshape(-1)
+                        r, s = self._fused_steps(self._prep(cx), yc, None, batch_size,
+                                                 nb if left is None else min(nb, left))
+                        rows += r
+                        steps += s
+                        continue
                     for s in range(0, len(cx), batch_size):
                         if steps_per_epoch is not None and steps >= steps_per_epoch:
                             done = True
